@@ -31,6 +31,9 @@ GPMP_BENCH_LIVE_PMC (1: two rocprofv3 counter passes of one step each measure ro
 (nccl; gloo = rehearsal on fewer GPUs than ranks), GPMP_BENCH_DIST (1), GPMP_BENCH_DIST_TIMEOUT (420 s), GPMP_BENCH_DIST_N,
 GPMP_BENCH_DIST_STRONG / GPMP_BENCH_DIST_MORE (1: the strong-scaling / predict + gradient parts of the distributed extra),
 GPMP_BENCH_STRONG_NM, GPMP_BENCH_HEADLINE_TIMEOUT (1500 s); tests: GPMP_BENCH_STUB_MODULE.
+--dump-outputs DIR: what the LAST timed step returned to its caller (posterior mean and variance, the NLL) is written to
+DIR/<name>.npy (float64; DIR/<name>_rank<r>.npy at N > 1), at most DUMP_BUDGET_BYTES in all -- a larger output is replaced by a
+fixed, seeded sample of its entries.  The inputs are seeded, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -56,6 +59,33 @@ def synth(n, m, d, rank):
     xt = np.random.default_rng(4321 + rank).random((m, d))
     theta = np.concatenate(([0.0], -np.log(0.5 * (1.0 + np.arange(d) / d))))
     return xi, zi, xt, theta
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1, budget=DUMP_BUDGET_BYTES):
+    """Write ``arrays`` ({name: float32 / float64 array}) as out_dir/<name>.npy (<name>_rank<r>.npy at world > 1).  If they
+    exceed this rank's share of ``budget``, every array is cut to the same fraction of its entries, taken at indices drawn
+    from a fixed seed (equal sizes -> equal indices), so that the files of two runs line up entry for entry.
+    -> {file name: shape written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    for k, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"dump_outputs: {k} has dtype {a.dtype}, expected float32 or float64")
+    share = budget // max(world, 1)
+    total = sum(a.nbytes for a in arrays.values())
+    written = {}
+    for k, a in arrays.items():
+        if total > share and a.size > 1:
+            keep = max(1, int(a.size * (share / total)))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        name = f"{k}.npy" if world == 1 else f"{k}_rank{rank}.npy"
+        np.save(os.path.join(out_dir, name), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def pmc_traffic_per_launch(kernel_substr):
@@ -1060,6 +1090,13 @@ class HipWorkload:
         self.out = (zpm, zpv, nll)
         return self.out
 
+    def outputs(self):
+        """host copies of what the last step returned: posterior mean and variance at the m points, the NLL"""
+        zpm, zpv, nll = self.out
+        return {"predict_mean": zpm.detach().to("cpu", self.torch.float64).numpy(),
+                "predict_variance": zpv.detach().to("cpu", self.torch.float64).numpy(),
+                "nll": np.array(float(nll), dtype=np.float64)}
+
     # HIP events on the launch stream around every launch of the DOMINANT kernel only (kind 9: the LDS-direct NN GEMM
     # of the n x m solve, 63 launches per step) inside the timed region; recording every kind (9000 events per step
     # around the small launches of the factorisations) costs 0.8 % of the step, so the other kinds are collected from
@@ -1233,9 +1270,12 @@ def headline_worker(args):
         wl.step()
     barrier()
     elapsed = time.perf_counter() - t0
+    # (outside the timed region; before timed_end, whose extra diagnostic step replaces the workload's last outputs)
+    last_outputs = getattr(wl, "outputs", dict)() if args.dump_outputs else None
     wl.timed_end()
     elapsed = max_over_ranks(elapsed)
     wl.check()
+    dumped = dump_outputs(args.dump_outputs, last_outputs, rank, world) if args.dump_outputs else None
 
     # ---- who ran: one PID per rank (evidence that N processes, not one, produced the line)
     pids = [os.getpid()]
@@ -1289,6 +1329,8 @@ def headline_worker(args):
             "ranks_seen": ranks_seen,
             "extra": {"worker_pids": pids, "backend": backend if dist_on else None, "strong_scaling": strong},
         }
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dumped}
         wl.report(line)
     if dist_on:
         dist.barrier()
@@ -1319,7 +1361,11 @@ def main():
     ap.add_argument("--no-live-pmc", action="store_true", help="do not run the two rocprofv3 --pmc child passes that measure roofline.traffic")
     ap.add_argument("--role", choices=("auto", "headline", "dist-extra", "cpu-full"), default="auto", help="internal: set by the launcher")
     ap.add_argument("--progress", default=None, help="internal: progress file of the distributed extra")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (at most 64 MB; module docstring)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.role == "dist-extra":
         return dist_extra_worker(args)
     if args.role == "cpu-full":

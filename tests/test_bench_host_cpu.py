@@ -63,3 +63,31 @@ def test_latest_committed_cpu_log_is_chosen_by_round_number(tmp_path, monkeypatc
                                                              "points_per_s": 4 / s, "threads": 16}) + "\n")
     monkeypatch.setattr(bench, "ROOT", str(tmp_path))
     assert bench._latest_cpu_fullsize_log(8, 4, 2)["s_per_step"] == 150.0        # r10 is later than r9 and r4
+
+
+def test_dump_outputs_writes_float_arrays_within_budget_and_samples_alike(tmp_path):
+    """--dump-outputs: small outputs are written whole; past the budget every array keeps the same seeded entries, so two
+    runs (or the mean and the variance of one run) line up entry for entry; per-rank names at world > 1"""
+    import bench
+
+    mean, var = np.arange(1000, dtype=np.float64), np.arange(1000, dtype=np.float64) * 2.0
+    got = bench.dump_outputs(str(tmp_path / "whole"), {"mean": mean, "var": var, "nll": np.array(1.5)})
+    assert got == {"mean.npy": [1000], "var.npy": [1000], "nll.npy": []}
+    assert np.array_equal(np.load(tmp_path / "whole" / "mean.npy"), mean) and float(np.load(tmp_path / "whole" / "nll.npy")) == 1.5
+
+    budget = 4000                               # bytes: 16 008 to write -> a quarter of each array
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"mean": mean, "var": var, "nll": np.array(1.5)}, budget=budget)
+    a_mean, a_var = np.load(tmp_path / "a" / "mean.npy"), np.load(tmp_path / "a" / "var.npy")
+    assert a_mean.nbytes + a_var.nbytes <= budget and a_mean.size > 0
+    assert np.array_equal(a_mean, np.load(tmp_path / "b" / "mean.npy"))
+    assert np.array_equal(a_var, 2.0 * a_mean) and np.all(np.diff(a_mean) > 0)       # same sorted indices in both arrays
+
+    got = bench.dump_outputs(str(tmp_path / "ranks"), {"mean": mean}, rank=1, world=2)
+    assert got == {"mean_rank1.npy": [1000]}
+    try:
+        bench.dump_outputs(str(tmp_path / "bad"), {"idx": np.arange(3)})
+    except TypeError:
+        pass
+    else:
+        raise AssertionError("integer outputs must be refused")

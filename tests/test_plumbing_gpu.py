@@ -287,6 +287,7 @@ def test_repeated_calls_do_not_grow_device_memory_host_memory_or_descriptors(gnp
     """400 rounds of every model-level entry point (predict with and without weights, NLL, REML, leave-one-out, criterion value and
     gradient) on the same inputs: allocated device bytes, the process's resident set and its open descriptors stay where they were
     after the warm-up (the library owns per-device streams / events / flag blocks; none may be created per call)."""
+    import gc
     import os
 
     import gpmp_amd as gp
@@ -316,12 +317,16 @@ def test_repeated_calls_do_not_grow_device_memory_host_memory_or_descriptors(gnp
         crit[1](th)
         crit[3](th)
 
+    # both readings after a full collection: device tensors that earlier tests left in reference cycles must not be freed
+    # half-way through the rounds and read as a change
     for _ in range(40):
         step()
     torch.cuda.synchronize()
+    gc.collect()
     a0, r0, f0 = torch.cuda.memory_allocated(), rss_mb(), len(os.listdir("/proc/self/fd"))
     for _ in range(400):
         step()
     torch.cuda.synchronize()
+    gc.collect()
     a1, r1, f1 = torch.cuda.memory_allocated(), rss_mb(), len(os.listdir("/proc/self/fd"))
     assert a1 == a0 and f1 == f0 and r1 - r0 < 20.0, (a0, a1, r0, r1, f0, f1)

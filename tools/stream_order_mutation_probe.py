@@ -10,6 +10,12 @@ Mutation test: the 2 x 4 grid of thread-ranks runs factorisation + NLL + predict
 and compares each with the single-GPU result.  Expected: intact agrees to rounding, both mutations do not (a fabric that
 synchronised the host around every message, as gloo does, would hide part of this).  Prints one line per case.
 
+A removed wait only shows if the work it guarded is still in flight when the consumer starts, and the host may take a whole step
+of the schedule (with its meetings of the eight thread-ranks) between enqueueing the two.  So every block of work on the PRODUCING
+stream starts with a GPU stall (``STALL_CYCLES``, longer than a host step): the side stream for mutated_main, the bulk stream for
+mutated_side.  The stalled stream falls further behind on every step, and the outcome no longer depends on how fast the host
+enqueues.  Each mutation has an intact run under the same stall beside it: the stall alone must not change the result.
+
     python tools/stream_order_mutation_probe.py
 """
 import math
@@ -19,6 +25,8 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+STALL_CYCLES = 50_000_000     # shader clock cycles (~20 ms) at the start of every block of work on the stalled stream
 
 
 def main():
@@ -41,8 +49,20 @@ def main():
     rm, rv = ref_model.predict(x, z, xt)
     rnll = float(ref_model.negative_log_likelihood_zero_mean(th, x, z))
     orig_wait = chmod._Streams.wait
+    orig_main_ctx, orig_side_ctx = chmod._Streams.main_ctx, chmod._Streams.side_ctx
 
-    def run_case(mutation, host_staged=False):
+    def stalled(orig_ctx, which):
+        def ctx(self):
+            if self.on:
+                with torch.cuda.stream(getattr(self, which)):
+                    torch.cuda._sleep(STALL_CYCLES)
+            return orig_ctx(self)
+        return ctx
+
+    # the stream each mutation no longer waits for: the producer of what the removed waits guarded
+    producer = {"mutated_main": "side", "mutated_side": "main"}
+
+    def run_case(mutation, stall, host_staged=False):
         out = {}
 
         def wait(self, side, ev):
@@ -53,6 +73,10 @@ def main():
             return orig_wait(self, side, ev)
 
         chmod._Streams.wait = wait
+        if stall == "main":
+            chmod._Streams.main_ctx = stalled(orig_main_ctx, "main")
+        else:
+            chmod._Streams.side_ctx = stalled(orig_side_ctx, "side")
         try:
             def body(rank, world, fabric, classes):
                 Ch = classes[0] if host_staged else classes[1]
@@ -72,33 +96,37 @@ def main():
             errors = thread_ranks.run(pr * pc, body, limit_s=240.0)
         finally:
             chmod._Streams.wait = orig_wait
+            chmod._Streams.main_ctx, chmod._Streams.side_ctx = orig_main_ctx, orig_side_ctx
         if errors:
-            return {"case": mutation, "error": errors[0].strip().splitlines()[-1][:200]}
+            return {"case": mutation, "stalled": stall, "error": errors[0].strip().splitlines()[-1][:200]}
         zpm = np.full(m, np.nan)
         for (r, a, b, mu, v, info, nll) in out.values():
             if mu is not None and r == 0:
                 zpm[a:b] = mu
         o = out[0]
-        return {"case": mutation, "info": int(o[5]), "nll_rel_diff": abs(o[6] - rnll) / abs(rnll) if o[5] == 0 else None,
+        return {"case": mutation, "stalled": stall, "info": int(o[5]), "nll_rel_diff": abs(o[6] - rnll) / abs(rnll) if o[5] == 0 else None,
                 "max_abs_dmean": float(np.nanmax(np.abs(zpm - rm))) if np.isfinite(zpm).any() else None}
 
     def agrees(res):
         return bool(res.get("info") == 0 and res.get("nll_rel_diff") is not None and res["nll_rel_diff"] < 1e-9 and res["max_abs_dmean"] < 1e-7)
 
     ok = True
-    for case in ("intact", "mutated_main", "mutated_side", "intact"):
-        res = run_case(case)
+    summary = []
+    for case, stall in (("intact", "side"), ("mutated_main", "side"), ("mutated_side", "main"), ("intact", "main")):
+        res = run_case(case, stall)
         res["fabric"] = "stream-ordered, device-resident"
         res["agrees_with_single_gpu"] = agrees(res)
         print(res, flush=True)
+        summary.append(f"{case}/{stall}-stalled agrees={res['agrees_with_single_gpu']}")
         ok = ok and (res["agrees_with_single_gpu"] == (case == "intact"))
     # the same mutations on the host-staged fabric (what a gloo run is): informational -- does a host synchronisation around
     # every message hide them?
     for case in ("mutated_main", "mutated_side"):
-        res = run_case(case, host_staged=True)
+        res = run_case(case, producer[case], host_staged=True)
         res["fabric"] = "host-staged (as over gloo)"
         res["agrees_with_single_gpu"] = agrees(res)
         print(res, flush=True)
+    print("stream-ordered fabric:", "; ".join(summary), flush=True)
     print("MUTATION PROBE", "OK: the stream-ordered fabric sees both missing dependencies and passes the intact schedule" if ok else "INCONCLUSIVE")
 
 
