@@ -152,7 +152,8 @@ def batch_values_and_gradients(model, covparams, batches, want_grad=True, use_me
     ns = [int(x.shape[0]) for x in xs] * (B if one_data else 1)
     d = int(xs[0].shape[1])
     nmax = max(ns)
-    if nmax > BATCH_MAX_N or any(int(x.shape[1]) != d for x in xs):
+    # (the batched driver keeps its parameters in fixed-width blocks: d <= 64; wider inputs go one problem at a time)
+    if nmax > BATCH_MAX_N or d > 64 or any(int(x.shape[1]) != d for x in xs):
         return None
     Ps, q = None, 0
     if use_mean:

@@ -258,7 +258,7 @@ def fused_prediction(model, xi, zi, xt):
     d = int(xi.shape[1])
     lib = gnp._lib.load()
     theta = gnp._host_params(model.covparam)
-    if d > 64 or cov.p > 16 or len(theta) != 1 + (1 if cov.noise else 0) + d:
+    if cov.p > 16 or len(theta) != 1 + (1 if cov.noise else 0) + d:
         return None
     zt_prior_mean = 0.0
     zc = gnp.asarray(zi).reshape(-1)

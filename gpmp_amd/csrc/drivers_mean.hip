@@ -184,7 +184,7 @@ __global__ void __launch_bounds__(256) rows_kernel(const double* __restrict__ X,
 // g[j] <- 1/2 g[j] (gpmp_matern_grad_trace returns the plain traces); zeros when the factorisation failed (the
 // criterion is +inf there and the selection wrappers return a zero gradient, numpy_backend.py:344-350)
 __global__ void grad_finalize2_kernel(double* g, int len, const int* info) {
-  const int j = threadIdx.x;
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j < len) g[j] = (*info != 0) ? 0.0 : 0.5 * g[j];
 }
 
@@ -227,7 +227,7 @@ int check_common(const double* x, const double* z, const double* P, long ldp, in
   GPMP_ARG(q >= 0 && q <= QMAX, 7, "q outside [0, GPMP_MAX_RANK - 1]");
   GPMP_ARG(q == 0 || (P != nullptr && ldp >= q), 3, "P is NULL or ldp < q");
   GPMP_ARG(n > q && n <= GPMP_MAX_EXTENT, 5, "n <= q or above GPMP_MAX_EXTENT");
-  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM, 6, "d outside [1, GPMP_MAX_DIM]");
+  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM_WIDE, 6, "d outside [1, GPMP_MAX_DIM_WIDE]");
   GPMP_ARG(theta_host != nullptr, 9, "theta is NULL");
   GPMP_ARG(ws != nullptr, 11, "ws is NULL");
   GPMP_ARG(info_dev != nullptr, 13, "info_dev is NULL");
@@ -392,7 +392,8 @@ extern "C" int gpmp_nll_grad(const double* x, const double* z, const double* P, 
   if (rc) return rc;
   rc = gpmp_matern_grad_trace(K, l.ldn, x, n, d, p, theta_host, noise, ws + l.F, ws + l.G, q + 1, l.ldq, grad_dev, ws + l.gws, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(grad_finalize2_kernel, dim3(1), dim3(128), 0, st, grad_dev, 1 + (noise ? 1 : 0) + d, info_dev);
+  const int glen = 1 + (noise ? 1 : 0) + d;
+  hipLaunchKernelGGL(grad_finalize2_kernel, dim3((glen + 127) / 128), dim3(128), 0, st, grad_dev, glen, info_dev);
   GPMP_HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -445,7 +446,7 @@ extern "C" int gpmp_predict_mean(const double* xi, const double* zi, const doubl
   GPMP_ARG(Pt != nullptr && ldpt >= q, 6, "Pt is NULL or ldpt < q");
   GPMP_ARG(n > q && n <= GPMP_MAX_EXTENT, 8, "n <= q or above GPMP_MAX_EXTENT");
   GPMP_ARG(m > 0 && m <= GPMP_MAX_EXTENT, 9, "m outside [1, GPMP_MAX_EXTENT]");
-  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM, 10, "d outside [1, GPMP_MAX_DIM]");
+  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM_WIDE, 10, "d outside [1, GPMP_MAX_DIM_WIDE]");
   GPMP_ARG(theta_host != nullptr, 13, "theta is NULL");
   GPMP_ARG(ws != nullptr, 16, "ws is NULL");
   GPMP_ARG(zpm_dev != nullptr && zpv_dev != nullptr, 17, "output is NULL");

@@ -9,86 +9,10 @@
 // row blocks are pre-scaled (2c / rho for the covariance, 1 / rho for the plain distance) while staged into LDS
 // ([k][128] and [k][64] images, 16 dimensions per chunk); each thread owns column pairs, so every store is 16 bytes
 // and the 16 lanes of a row write 256 contiguous bytes.  The gradient-trace pass keeps 64 x 64 tiles (GT).
-#include "common.h"
-#include <cmath>
+#include "matern_device.h"
 
 namespace gpmp {
 namespace {
-
-constexpr int GT = 64;   // tile edge
-constexpr int DC = 16;   // dimensions per LDS chunk
-
-struct MaternSpec {
-  int p;
-  double c;                      // 2 sqrt(p + 1/2)
-  double q[GPMP_MAX_P + 1];      // K(h) = exp(-t/2) sum_k q[k] t^k, t = 2 c h
-  double s[GPMP_MAX_P + 1];      // (dK/dh)/h = (2c)^2 exp(-t/2) sum_{k>=1} s[k] t^(k-1)   (p >= 1)
-};
-
-
-__device__ __forceinline__ double matern_eval(const MaternSpec& ms, double h) {
-  // maternp_kernel, gpmp/kernel/matern.py:54-64 (Horner form of the same polynomial).
-  const double t = 2.0 * ms.c * h;
-  double poly = ms.q[ms.p];
-  for (int k = ms.p - 1; k >= 0; --k) poly = poly * t + ms.q[k];
-  return exp(-ms.c * h) * poly;
-}
-
-template <int P>
-__device__ __forceinline__ double matern_eval_p(const MaternSpec& ms, double h) {
-  const double t = 2.0 * ms.c * h;
-  double poly = ms.q[P];
-#pragma unroll
-  for (int k = P - 1; k >= 0; --k) poly = poly * t + ms.q[k];
-  return exp(-ms.c * h) * poly;
-}
-
-__device__ __forceinline__ double matern_dispatch(const MaternSpec& ms, double h) {
-  switch (ms.p) {
-    case 0: return matern_eval_p<0>(ms, h);
-    case 1: return matern_eval_p<1>(ms, h);
-    case 2: return matern_eval_p<2>(ms, h);
-    case 3: return matern_eval_p<3>(ms, h);
-    case 4: return matern_eval_p<4>(ms, h);
-    default: return matern_eval(ms, h);
-  }
-}
-
-// ---- fp64 helpers tuned for this kernel (VALU-bound: every instruction per entry counts) ---------------------------
-// All constants below travel in the kernel-argument struct: they are then loaded once into SGPRs and used as the
-// scalar operand of v_fma_f64.  As C++ literals the compiler re-materialised them into VGPRs next to every use
-// (22 v_mov per entry in the previous version of this kernel: a quarter of its VALU work).
-struct FastExp {
-  double nl2e_half;        // -log2(e) / 2
-  double ln2x2_hi, ln2x2_lo;  // 2 ln 2 split so that k * hi is exact for |k| < 2^20
-  double c[13];            // c[j] = 1 / (2^j j!)  -- exp(r/2) = sum_j c[j] r^j
-  double tiny;             // 1e-280, added to the rsq argument (a no-op for every normal a, keeps a == 0 finite)
-};
-
-// Per entry (inlined in the kernel, four entries in lock step):
-//  * sqrt(a), a >= 0: hardware 1/sqrt estimate of a + tiny (a == 0 then gives 0 without a select; NaN / inf still
-//    propagate through a), one coupled Newton step, one residual correction;
-//  * exp(-t/2), t >= 0: k = rint(t log2(e) / 2), r = 2 k ln2 - t in [-0.694, 0.694], exp(r/2) by a degree-12 Taylor
-//    polynomial in r (remainder 0.347^13 / 13! = 1.7e-16), scaled by 2^-k: < 1 ulp of libm on [0, 745], exact 1 at 0.
-__device__ __forceinline__ double fast_sqrt_pos(double a, double tiny) {
-  const double y0 = __builtin_amdgcn_rsq(a + tiny);
-  double g = a * y0, h = 0.5 * y0;
-  const double r = fma(-h, g, 0.5);
-  g = fma(g, r, g);
-  h = fma(h, r, h);
-  const double d = fma(-g, g, a);
-  return fma(d, h, g);
-}
-__device__ __forceinline__ double fast_exp_neg_half(const FastExp& fe, double t) {
-  const double nk = rint(t * fe.nl2e_half);                 // -k
-  double r = fma(-nk, fe.ln2x2_hi, -t);
-  r = fma(-nk, fe.ln2x2_lo, r);
-  double e = fe.c[12];
-#pragma unroll
-  for (int j = 11; j >= 0; --j) e = fma(e, r, fe.c[j]);
-  const int k = (int)nk;
-  return ldexp(e, k < -1100 ? -1100 : k);
-}
 
 struct GramParams {
   const double* x;
@@ -270,18 +194,6 @@ __global__ void __launch_bounds__(256) gram_kernel_v3(GramParams p) {
   }
 }
 
-static void fill_fast_exp(FastExp& fe) {
-  fe.nl2e_half = -0.5 * 1.4426950408889634;
-  fe.ln2x2_hi = 2.0 * 6.93147180369123816490e-01;
-  fe.ln2x2_lo = 2.0 * 1.90821492927058770002e-10;
-  fe.tiny = 1e-280;
-  double f = 1.0;
-  for (int j = 0; j <= 12; ++j) {
-    if (j) f *= 2.0 * j;         // 2^j j!  (exact in fp64 up to j = 12: 1.96e12)
-    fe.c[j] = 1.0 / f;
-  }
-}
-
 static int launch_gram(const GramParams& gp, hipStream_t st) {
   dim3 grid((gp.m + GT - 1) / GT, (gp.n + 127) / 128, gp.nprob > 1 ? gp.nprob : 1);
   if (gp.mode != 0) {
@@ -366,18 +278,6 @@ struct GradParams {
   MaternSpec ms;
   FastExp fe;
 };
-
-__device__ __forceinline__ double matern_dk_over_h(const MaternSpec& ms, double h, double& kval) {
-  const double t = 2.0 * ms.c * h;
-  const double e = exp(-ms.c * h);
-  double poly = ms.q[ms.p];
-  for (int k = ms.p - 1; k >= 0; --k) poly = poly * t + ms.q[k];
-  kval = e * poly;
-  if (ms.p == 0) return h > 0.0 ? -ms.c * e / h : 0.0;
-  double s = ms.s[ms.p];
-  for (int k = ms.p - 1; k >= 1; --k) s = s * t + ms.s[k];
-  return (2.0 * ms.c) * (2.0 * ms.c) * e * s;
-}
 
 // PP: length scales from the problem's parameter block in device memory instead of the kernel arguments (a run-time choice
 // between the two sources made the compiler copy the argument block to scratch memory: compile-time instead)
@@ -621,22 +521,6 @@ __global__ void gram_deriv_kernel(DerivParams p) {
   p.out[(long)i * p.ld + k] = v;
 }
 
-// ---- host-side helpers -------------------------------------------------------------------------
-int fill_matern(MaternSpec& ms, int p) {
-  if (p < 0 || p > GPMP_MAX_P) return -1;
-  ms.p = p;
-  ms.c = 2.0 * std::sqrt(p + 0.5);
-  for (int k = 0; k <= GPMP_MAX_P; ++k) ms.q[k] = ms.s[k] = 0.0;
-  ms.q[0] = 1.0;
-  for (int i = 0; i < p; ++i) {  // a_i multiplies t^(p-i), gpmp/kernel/matern.py:59-63
-    const double a = std::exp(std::lgamma(p + 1.0) - std::lgamma(2.0 * p + 1.0) + std::lgamma(p + i + 1.0) -
-                              std::lgamma(i + 1.0) - std::lgamma(p - i + 1.0));
-    ms.q[p - i] = a;
-  }
-  for (int k = 0; k <= p; ++k) ms.s[k] = (k + 1 <= p ? (k + 1) * ms.q[k + 1] : 0.0) - 0.5 * ms.q[k];
-  return 0;
-}
-
 }  // namespace
 }  // namespace gpmp
 
@@ -648,13 +532,24 @@ extern "C" int gpmp_matern_gram(const double* x, const double* y, int n, int m, 
   GPMP_ARG(x != nullptr, 1, "x is NULL");
   GPMP_ARG(n >= 0 && n <= GPMP_MAX_EXTENT, 3, "n outside [0, GPMP_MAX_EXTENT]");
   GPMP_ARG(m >= 0 && m <= GPMP_MAX_EXTENT, 4, "m outside [0, GPMP_MAX_EXTENT]");
-  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM, 5, "d outside [1, GPMP_MAX_DIM]");
+  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM_WIDE, 5, "d outside [1, GPMP_MAX_DIM_WIDE]");
   GPMP_ARG(p >= 0 && p <= GPMP_MAX_P, 6, "p outside [0, GPMP_MAX_P]");
   GPMP_ARG(theta_host != nullptr, 7, "theta is NULL");
   GPMP_ARG(K != nullptr, 11, "K is NULL");
   if (y == nullptr) m = n;
   GPMP_ARG(ldk >= m, 12, "ldk < m");
   if (n == 0 || m == 0) return 0;
+  if (d > GPMP_MAX_DIM) {
+    MaternSpec ms;
+    fill_matern(ms, p);
+    const double sigma2 = std::exp(theta_host[0]);
+    const int off = noise ? 2 : 1;
+    auto* scale = new std::vector<double>(d);
+    for (int k = 0; k < d; ++k) (*scale)[k] = 2.0 * ms.c * std::exp(theta_host[off + k]);
+    double q[GPMP_MAX_P + 1];
+    for (int k = 0; k <= GPMP_MAX_P; ++k) q[k] = sigma2 * ms.q[k];
+    return gram_wide(x, y, n, m, d, 0, p, scale, q, diag_add, lower_only, K, ldk, as_stream(stream));
+  }
   GramParams gp;
   gp.nprob = 1; gp.stride_x = gp.stride_k = 0; gp.ns = nullptr; gp.pp = nullptr;
   gp.x = x; gp.y = y; gp.K = K; gp.ldk = ldk;
@@ -684,11 +579,17 @@ extern "C" int gpmp_scaled_distance(const double* x, const double* y, int n, int
                                     const double* loginvrho_host, double* D, long ldd,
                                     gpmp_stream_t stream) {
   GPMP_ARG(x != nullptr && y != nullptr, 1, "x or y is NULL");
-  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM, 5, "d outside [1, GPMP_MAX_DIM]");
+  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM_WIDE, 5, "d outside [1, GPMP_MAX_DIM_WIDE]");
   GPMP_ARG(loginvrho_host != nullptr, 6, "loginvrho is NULL");
   GPMP_ARG(D != nullptr && ldd >= m, 7, "D is NULL or ldd < m");
   GPMP_ARG(n <= GPMP_MAX_EXTENT && m <= GPMP_MAX_EXTENT, 3, "n or m above GPMP_MAX_EXTENT");
   if (n <= 0 || m <= 0) return 0;
+  if (d > GPMP_MAX_DIM) {
+    auto* scale = new std::vector<double>(d);
+    for (int k = 0; k < d; ++k) (*scale)[k] = std::exp(loginvrho_host[k]);
+    const double q[GPMP_MAX_P + 1] = {};
+    return gram_wide(x, y, n, m, d, 1, 0, scale, q, 0.0, 0, D, ldd, as_stream(stream));
+  }
   GramParams gp;
   gp.nprob = 1; gp.stride_x = gp.stride_k = 0; gp.ns = nullptr; gp.pp = nullptr;
   gp.x = x; gp.y = y; gp.K = D; gp.ldk = ldd;
@@ -708,12 +609,18 @@ extern "C" int gpmp_matern_pairwise(const double* x, const double* y, int n, int
                                     const double* theta_host, int noise, double* out,
                                     gpmp_stream_t stream) {
   GPMP_ARG(x != nullptr, 1, "x is NULL");
-  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM, 4, "d outside [1, GPMP_MAX_DIM]");
+  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM_WIDE, 4, "d outside [1, GPMP_MAX_DIM_WIDE]");
   GPMP_ARG(p >= 0 && p <= GPMP_MAX_P, 5, "p outside [0, GPMP_MAX_P]");
   GPMP_ARG(theta_host != nullptr, 6, "theta is NULL");
   GPMP_ARG(out != nullptr, 8, "out is NULL");
   GPMP_ARG(n <= GPMP_MAX_EXTENT, 3, "n above GPMP_MAX_EXTENT");
   if (n <= 0) return 0;
+  if (d > GPMP_MAX_DIM) {
+    const int off = noise ? 2 : 1;
+    auto* invrho = new std::vector<double>(d);
+    for (int k = 0; k < d; ++k) (*invrho)[k] = std::exp(theta_host[off + k]);
+    return pairwise_wide(x, y, n, d, p, std::exp(theta_host[0]), invrho, out, as_stream(stream));
+  }
   PairParams pp;
   pp.x = x; pp.y = y; pp.out = out; pp.n = n; pp.d = d; pp.same = (y == nullptr || y == x);
   pp.sigma2 = std::exp(theta_host[0]);
@@ -760,6 +667,7 @@ int launch_grad(GradParams& gp, int nblocks, hipStream_t st) {
 }  // namespace
 
 extern "C" size_t gpmp_grad_ws_elems(int n, int d) {
+  if (d > GPMP_MAX_DIM) return d <= GPMP_MAX_DIM_WIDE ? grad_wide_ws_elems(n, d) : 0;
   (void)n;
   return (size_t)GRAD_BLOCKS * (grad_tier(d) + 2);
 }
@@ -890,12 +798,21 @@ extern "C" int gpmp_matern_grad_trace(const double* Kinv, long ldk, const double
   GPMP_ARG(x != nullptr, 3, "x is NULL");
   GPMP_ARG(n >= 1 && n <= GPMP_MAX_EXTENT, 4, "n outside [1, GPMP_MAX_EXTENT]");
   GPMP_ARG(ldk >= n, 2, "ldk < n");
-  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM, 5, "d outside [1, GPMP_MAX_DIM]");
+  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM_WIDE, 5, "d outside [1, GPMP_MAX_DIM_WIDE]");
   GPMP_ARG(p >= 0 && p <= GPMP_MAX_P, 6, "p outside [0, GPMP_MAX_P]");
   GPMP_ARG(theta_host != nullptr, 7, "theta is NULL");
   GPMP_ARG(r >= 0 && r <= GPMP_MAX_RANK, 11, "r outside [0, GPMP_MAX_RANK]");
   GPMP_ARG(r == 0 || (F != nullptr && G != nullptr && ldf >= r), 9, "F/G NULL or ldf < r with r > 0");
   GPMP_ARG(g_dev != nullptr && ws != nullptr, 13, "g or ws is NULL");
+  if (d > GPMP_MAX_DIM) {
+    MaternSpec ms;
+    fill_matern(ms, p);
+    const int off = noise ? 2 : 1;
+    auto* scale = new std::vector<double>(d);
+    for (int k = 0; k < d; ++k) (*scale)[k] = 2.0 * ms.c * std::exp(theta_host[off + k]);
+    return grad_trace_wide(Kinv, ldk, x, n, nullptr, 0, d, p, std::exp(theta_host[0]), noise, noise ? std::exp(theta_host[1]) : 0.0,
+                           scale, F, G, r, ldf, g_dev, ws, 0, as_stream(stream));
+  }
   GradParams gp;
   gp.pp = nullptr;
   gp.nprob = 1; gp.stride_kinv = gp.stride_x = gp.stride_f = gp.stride_partial = 0; gp.ns = nullptr;
@@ -947,12 +864,21 @@ extern "C" int gpmp_matern_grad_trace_cross(const double* M, long ldm, const dou
   GPMP_ARG(M != nullptr, 1, "M is NULL");
   GPMP_ARG(x != nullptr && y != nullptr, 3, "x or y is NULL");
   GPMP_ARG(n >= 1 && m >= 1 && n <= GPMP_MAX_EXTENT && m <= GPMP_MAX_EXTENT && ldm >= m, 4, "n or m outside [1, GPMP_MAX_EXTENT], or ldm < m");
-  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM, 7, "d outside [1, GPMP_MAX_DIM]");
+  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM_WIDE, 7, "d outside [1, GPMP_MAX_DIM_WIDE]");
   GPMP_ARG(p >= 0 && p <= GPMP_MAX_P, 8, "p outside [0, GPMP_MAX_P]");
   GPMP_ARG(theta_host != nullptr, 9, "theta is NULL");
   GPMP_ARG(r >= 0 && r <= GPMP_MAX_RANK, 13, "r outside [0, GPMP_MAX_RANK]");
   GPMP_ARG(r == 0 || (F != nullptr && G != nullptr && ldf >= r), 11, "F/G NULL or ldf < r with r > 0");
   GPMP_ARG(g_dev != nullptr && ws != nullptr, 15, "g or ws is NULL");
+  if (d > GPMP_MAX_DIM) {
+    MaternSpec ms;
+    fill_matern(ms, p);
+    const int off = noise ? 2 : 1;
+    auto* scale = new std::vector<double>(d);
+    for (int k = 0; k < d; ++k) (*scale)[k] = 2.0 * ms.c * std::exp(theta_host[off + k]);
+    return grad_trace_wide(M, ldm, x, n, y, m, d, p, std::exp(theta_host[0]), noise, 0.0, scale, F, G, r, ldf, g_dev, ws, 1,
+                           as_stream(stream));
+  }
   GradParams gp;
   gp.pp = nullptr;
   gp.nprob = 1; gp.stride_kinv = gp.stride_x = gp.stride_f = gp.stride_partial = 0; gp.ns = nullptr;
@@ -997,12 +923,21 @@ extern "C" int gpmp_matern_gram_deriv(const double* x, int n, int d, int p, cons
                                       int jparam, double* out, long ld, gpmp_stream_t stream) {
   GPMP_ARG(x != nullptr, 1, "x is NULL");
   GPMP_ARG(n >= 1 && n <= 65535, 2, "n outside [1, 65535] (diagnostic-sized problems)");
-  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM, 3, "d outside [1, GPMP_MAX_DIM]");
+  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM_WIDE, 3, "d outside [1, GPMP_MAX_DIM_WIDE]");
   GPMP_ARG(p >= 0 && p <= GPMP_MAX_P, 4, "p outside [0, GPMP_MAX_P]");
   GPMP_ARG(theta_host != nullptr, 5, "theta is NULL");
   const int off = noise ? 2 : 1;
   GPMP_ARG(jparam >= 0 && jparam < off + d, 7, "jparam outside the parameter vector");
   GPMP_ARG(out != nullptr && ld >= n, 8, "out is NULL or ld < n");
+  if (d > GPMP_MAX_DIM) {
+    const double sigma2 = std::exp(theta_host[0]);
+    const double eps = 2.220446049250313e-16;
+    auto* invrho = new std::vector<double>(d);
+    for (int k = 0; k < d; ++k) (*invrho)[k] = std::exp(theta_host[off + k]);
+    if (jparam == 0) return gram_deriv_wide(x, n, d, p, 0, -1, sigma2, noise ? 0.0 : 10.0 * sigma2 * eps, invrho, out, ld, as_stream(stream));
+    if (noise && jparam == 1) return gram_deriv_wide(x, n, d, p, 1, -1, sigma2, std::exp(theta_host[1]), invrho, out, ld, as_stream(stream));
+    return gram_deriv_wide(x, n, d, p, 2, jparam - off, sigma2, 0.0, invrho, out, ld, as_stream(stream));
+  }
   DerivParams dp;
   dp.x = x; dp.out = out; dp.ld = ld; dp.n = n; dp.d = d;
   dp.sigma2 = std::exp(theta_host[0]);

@@ -32,6 +32,10 @@
  *    GPU; SEVERAL host threads on ONE device (eight thread-ranks of the distributed tests share a GPU); the per-device table
  *    under the host sanitizers (gpmp_debug_device_table_selftest).  NOT tested: more than one device ordinal driven from
  *    one process -- the GPU pool this was developed on has one-GPU boxes.
+ *  - INPUT DIMENSION: every entry point that takes d accepts 1 <= d <= GPMP_MAX_DIM_WIDE (except the batched small-problem
+ *    driver, d <= GPMP_MAX_DIM).  d <= GPMP_MAX_DIM runs the register-tier kernels (length scales in the kernel arguments);
+ *    larger d runs the wide-dimension kernels, whose length scales are copied to a stream-ordered device allocation per call
+ *    (hipMallocAsync / hipFreeAsync on `stream`; for the gradient trace, inside the caller's workspace).
  *  - covparam layout (gpmp/kernel/matern.py:78-79,88-89): theta = [log sigma^2, log(1/rho_1..d)];
  *    with `noise` != 0 the layout is [log sigma^2, log sigma_noise^2, log(1/rho_1..d)]
  *    (examples/gpmp_example07_nd_regression.py:95-131).
@@ -48,7 +52,9 @@ extern "C" {
 typedef void* gpmp_stream_t;
 
 #define GPMP_NB 128          /* diagonal block size of the blocked factorisation */
-#define GPMP_MAX_DIM 64      /* largest input dimension d handled by the Gram kernels */
+#define GPMP_MAX_DIM 64      /* largest input dimension d of the register-tier kernels (length scales in the kernel arguments);
+                                every entry point sends larger d to the wide-dimension kernels (length scales in device memory) */
+#define GPMP_MAX_DIM_WIDE 16384 /* largest input dimension d any entry point accepts */
 #define GPMP_MAX_P 16        /* largest Matern half-integer index p (nu = p + 1/2) */
 #define GPMP_MAX_RANK 72     /* largest low-rank correction width in gpmp_matern_grad_trace */
 #define GPMP_MAX_EXTENT (1 << 30) /* largest row / column / contraction count any entry point accepts: element OFFSETS are 64-bit
@@ -237,7 +243,8 @@ int gpmp_logdet_chol(const double* L, int n, long ldl, double* out_dev, gpmp_str
  *   M[i,k] = Kinv[i,k] - sum_{a<r} F[i,a] * G[k,a]     (Kinv: lower triangle used, symmetric)
  * and K the covariance of gpmp_matern_gram (ii path, diag_add = nugget or noise).  The reference has
  * no analytic form (torch autograd, gpmp/num/torch_backend.py:574-604); formulas in DESIGN.md.
- * ws: gpmp_grad_ws_elems(n, d) doubles.  Enqueue only. */
+ * ws: gpmp_grad_ws_elems(n, d) doubles (d > GPMP_MAX_DIM: per-workgroup partials of width d + 2 and the d length-scale
+ * factors; 0 when d is outside [1, GPMP_MAX_DIM_WIDE]).  Enqueue only. */
 int gpmp_matern_grad_trace(const double* Kinv, long ldk, const double* x, int n, int d, int p,
                            const double* theta_host, int noise, const double* F, const double* G,
                            int r, long ldf, double* g_dev, double* ws, gpmp_stream_t stream);
