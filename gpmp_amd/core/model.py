@@ -9,7 +9,7 @@ the Cholesky route; ``fisher_information_torch`` differentiates the HIP log-det 
 import warnings
 
 from .. import num as gnp
-from . import fisher, kriging, likelihood, linalg, loo, sample_paths, utils
+from . import fisher, kriging, likelihood, linalg, loo, predict_grad, sample_paths, utils
 
 
 class Model:
@@ -71,6 +71,24 @@ class Model:
         if return_lambdas:
             return (zt_posterior_mean, zt_posterior_variance, lambda_t)
         return (zt_posterior_mean, zt_posterior_variance)
+
+    def predict_gradient(self, xi, zi, xt, variance=True, mean_gradient=None, zero_neg_variances=True, convert_in=True,
+                         convert_out=True):
+        """Posterior mean and variance at xt and their gradients with respect to xt: ``(zpm, zpv, dzpm, dzpv)``, the gradients of
+        shape (m, d), ``dzpv`` None when ``variance`` is False (no second n^2 m solve then).  Replaces ``xt.requires_grad_()`` +
+        autograd through ``predict`` on the reference's torch backend.  Matern covariances (gpmp_amd.kernel.MaternCovariance) with
+        a zero, parameterized or linear-predictor mean; any other covariance raises NotImplementedError (``gnp.grad`` is the
+        finite-difference route).  ``mean_gradient(x, meanparam)``: the Jacobian of the mean, (m, q, d) ((m, d) for a
+        parameterized mean); without it the mean is differentiated by torch autograd, row t depending on x_t only.  xt is always
+        treated as new points (no identity dispatch for ``xt is xi``); where a negative variance is clamped to 0 its gradient
+        row is 0."""
+        xi, zi, xt = utils.ensure_shapes_and_type(xi=xi, zi=zi, xt=xt, convert=convert_in)
+        zpm, zpv, dzpm, dzpv = predict_grad.predict_gradient(self, xi, zi, xt, variance=variance, mean_gradient=mean_gradient,
+                                                             zero_neg_variances=zero_neg_variances)
+        if convert_out:
+            zpm, zpv, dzpm = gnp.to_np(zpm), gnp.to_np(zpv), gnp.to_np(dzpm)
+            dzpv = None if dzpv is None else gnp.to_np(dzpv)
+        return zpm, zpv, dzpm, dzpv
 
     def loo(self, xi, zi, convert_in=True, convert_out=False):
         """Leave-one-out predictions -- gpmp/core/model.py:309-343."""

@@ -331,6 +331,91 @@ PredictMeanLayout predict_mean_layout(int n, int m, int q) {
   return l;
 }
 
+
+// ---- gradient of the prediction with respect to the prediction points (gpmp_predict_grad) --------------------------------
+// Per point t, as predict_mean_finalize_kernel, plus mu_t = S^-1 r_t (q x m, ld ldmu) and the unclamped variance (q = 0: no r).
+__global__ void __launch_bounds__(256) pgrad_point_kernel(const double* __restrict__ D, long ldd, const double* __restrict__ Pt,
+                                                          long ldpt, int m, int q, const double* __restrict__ Sinv, long lds,
+                                                          const double* __restrict__ small, double sigma2, int clamp, const int* info,
+                                                          double* __restrict__ zpm, double* __restrict__ zpv, double* __restrict__ vraw,
+                                                          double* __restrict__ mu, long ldmu) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  double mean = D[j], quad = 0.0;
+  for (int a = 0; a < q; ++a) {
+    double ta = 0.0;
+    for (int b = 0; b < q; ++b) ta += Sinv[(long)a * lds + b] * (D[(long)(1 + b) * ldd + j] - Pt[(long)j * ldpt + b]);
+    const double ra = D[(long)(1 + a) * ldd + j] - Pt[(long)j * ldpt + a];
+    mean -= small[SM_C + a] * ra;
+    quad += ra * ta;
+    mu[(long)a * ldmu + j] = ta;
+  }
+  const double v = sigma2 - (D[(long)(1 + q) * ldd + j] - quad);
+  vraw[j] = v;
+  const bool bad = *info != 0;
+  const double nan = __builtin_nan("");
+  zpm[j] = bad ? nan : mean;
+  zpv[j] = bad ? nan : ((clamp && v < 0.0) ? 0.0 : v);
+}
+
+// y_i = w_i - Wp_i . beta   (beta = S^-1 Wp^T w = small[SM_C]); K^-1 y is the weight vector of the mean gradient
+__global__ void pgrad_gamma_kernel(const double* __restrict__ W, long ldw, int n, int q, const double* __restrict__ small,
+                                   double* __restrict__ y) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double v = W[(long)i * ldw];
+  for (int a = 0; a < q; ++a) v -= W[(long)i * ldw + 1 + a] * small[SM_C + a];
+  y[i] = v;
+}
+
+// gm[t][j] += beta . J[t][:, j];   gv[t][j] = -2 gv[t][j] - 2 mu_t . J[t][:, j]  (0 where the variance was clamped); NaN on failure
+__global__ void pgrad_finalize_kernel(double* __restrict__ gm, double* __restrict__ gv, const double* __restrict__ J, int m, int d, int q,
+                                      const double* __restrict__ small, const double* __restrict__ mu, long ldmu,
+                                      const double* __restrict__ vraw, int clamp, const int* info) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)m * d) return;
+  const int t = (int)(idx / d), j = (int)(idx - (long)t * d);
+  const bool bad = *info != 0;
+  const double nan = __builtin_nan("");
+  double g = gm[idx];
+  for (int a = 0; a < q; ++a) g += small[SM_C + a] * J[((long)t * q + a) * d + j];
+  gm[idx] = bad ? nan : g;
+  if (gv != nullptr) {
+    double h = -2.0 * gv[idx];
+    for (int a = 0; a < q; ++a) h -= 2.0 * mu[(long)a * ldmu + t] * J[((long)t * q + a) * d + j];
+    if (clamp && vraw[t] < 0.0) h = 0.0;
+    gv[idx] = bad ? nan : h;
+  }
+}
+
+struct PredictGradLayout {
+  long ldn, ldm, ldq;
+  size_t K, dinv, Kit, Gm, PtP, Sinv, small, D, cd, y, vraw, mu, red, total;
+};
+PredictGradLayout predict_grad_layout(int n, int m, int d, int q) {
+  PredictGradLayout l;
+  l.ldn = pad16(n);
+  l.ldm = pad16(m + 2 + q);          // K(xi, xt) | z | P | (a zero column when that keeps the column count even)
+  l.ldq = pad16(1 + q);
+  size_t o = 0;
+  auto take = [&](size_t cnt) { size_t at = o; o += (size_t)pad16((long)cnt); return at; };
+  l.K = take((size_t)n * l.ldn);
+  l.dinv = take(gpmp_dinv_elems(n));
+  l.Kit = take((size_t)n * l.ldm);
+  l.Gm = take((size_t)(2 + q) * l.ldq);
+  l.PtP = take((size_t)(1 + q) * l.ldq);
+  l.Sinv = take((size_t)(q > 0 ? q : 1) * l.ldq);
+  l.small = take(SM_TOTAL);
+  l.D = take((size_t)(2 + q) * l.ldm);
+  const size_t cols = (size_t)(m > 1 + q ? m : 1 + q);
+  l.cd = take(cols * (size_t)gpmp_coldots_ws_rows(n));
+  l.y = take((size_t)n);
+  l.vraw = take((size_t)m);
+  l.mu = take((size_t)(q > 0 ? q : 1) * l.ldm);
+  l.red = take(gpmp_predict_grad_reduce_ws_elems(n, m, d));
+  l.total = o;
+  return l;
+}
 }  // namespace
 }  // namespace gpmp
 
@@ -494,6 +579,97 @@ extern "C" int gpmp_predict_mean(const double* xi, const double* zi, const doubl
                                    (int)(sizeof(double) * ((size_t)QMAX * QMAX + QMAX))));
   hipLaunchKernelGGL(predict_mean_finalize_kernel, dim3((m + 255) / 256), dim3(256), fin_bytes, st, ws + l.D, l.ldm, Pt, ldpt, m, q,
                      ws + l.Sinv, l.ldq, ws + l.small, sigma2, zero_neg_variances, info_dev, zpm_dev, zpv_dev);
+  GPMP_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" size_t gpmp_predict_grad_ws_elems(int n, int m, int d, int q) {
+  if (n < 1 || n > GPMP_MAX_EXTENT || m < 1 || m > GPMP_MAX_EXTENT || d < 1 || d > GPMP_MAX_DIM_WIDE || q < 0 || q > QMAX) return 0;
+  return predict_grad_layout(n, m, d, q).total;
+}
+
+extern "C" int gpmp_predict_grad(const double* xi, const double* zi, const double* Pi, long ldpi, const double* xt, const double* Pt,
+                                 long ldpt, const double* J, int n, int m, int d, int q, int p, const double* theta_host, int noise,
+                                 int zero_neg_variances, int with_variance_gradient, double* ws, double* zpm_dev, double* zpv_dev,
+                                 double* gzpm_dev, double* gzpv_dev, int* info_dev, gpmp_stream_t stream) {
+  GPMP_ARG(xi != nullptr, 1, "xi is NULL");
+  GPMP_ARG(zi != nullptr, 2, "zi is NULL");
+  GPMP_ARG(q >= 0 && q <= QMAX, 12, "q outside [0, GPMP_MAX_RANK - 1]");
+  GPMP_ARG(q == 0 || (Pi != nullptr && ldpi >= q), 3, "Pi is NULL or ldpi < q");
+  GPMP_ARG(xt != nullptr, 5, "xt is NULL");
+  GPMP_ARG(q == 0 || (Pt != nullptr && ldpt >= q), 6, "Pt is NULL or ldpt < q");
+  GPMP_ARG(q == 0 || J != nullptr, 8, "J is NULL with q > 0");
+  GPMP_ARG(n > q && n <= GPMP_MAX_EXTENT, 9, "n <= q or above GPMP_MAX_EXTENT");
+  GPMP_ARG(m > 0 && m <= GPMP_MAX_EXTENT, 10, "m outside [1, GPMP_MAX_EXTENT]");
+  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM_WIDE, 11, "d outside [1, GPMP_MAX_DIM_WIDE]");
+  GPMP_ARG(p >= 0 && p <= GPMP_MAX_P, 13, "p outside [0, GPMP_MAX_P]");
+  GPMP_ARG(theta_host != nullptr, 14, "theta is NULL");
+  GPMP_ARG(ws != nullptr, 18, "ws is NULL");
+  GPMP_ARG(zpm_dev != nullptr && zpv_dev != nullptr, 19, "zpm or zpv is NULL");
+  GPMP_ARG(gzpm_dev != nullptr, 21, "gzpm is NULL");
+  GPMP_ARG(with_variance_gradient == 0 || gzpv_dev != nullptr, 22, "gzpv is NULL with with_variance_gradient != 0");
+  GPMP_ARG(info_dev != nullptr, 23, "info_dev is NULL");
+  hipStream_t st = as_stream(stream);
+  const PredictGradLayout l = predict_grad_layout(n, m, d, q);
+  double* K = ws + l.K;
+  double* dinv = ws + l.dinv;
+  double* Kit = ws + l.Kit;
+  const double sigma2 = std::exp(theta_host[0]);
+  const double diag = noise ? std::exp(theta_host[1]) : 10.0 * sigma2 * DBL_EPSILON;   // matern.py:90
+  int rc = gpmp_matern_gram(xi, nullptr, n, n, d, p, theta_host, noise, diag, 1, K, l.ldn, stream);
+  if (rc) return rc;
+  rc = gpmp_matern_gram(xi, xt, n, m, d, p, theta_host, noise, 0.0, 0, Kit, l.ldm, stream);
+  if (rc) return rc;
+  // [V | w | Wp] = L^-1 [K(xi, xt) | z | P] in one solve, as gpmp_predict_mean
+  double* W = Kit + m;
+  const long ldw = l.ldm;
+  const int mb = (m + 1 + q) + ((m + 1 + q) & 1);
+  hipLaunchKernelGGL(pack_zp_kernel, dim3((n + 255) / 256), dim3(256), 0, st, zi, Pi, ldpi, n, q, W, ldw);
+  GPMP_HIP_TRY(hipGetLastError());
+  if (mb > m + 1 + q) GPMP_HIP_TRY(hipMemset2DAsync(Kit + m + 1 + q, (size_t)l.ldm * sizeof(double), 0, sizeof(double), n, st));
+  rc = gpmp_potrf_trsm_lower_async(K, n, l.ldn, dinv, info_dev, Kit, mb, l.ldm, stream);
+  if (rc) return rc;
+  if (q > 0) {
+    rc = gpmp_coldots(W, n, 1 + q, ldw, W, 1 + q, ldw, ws + l.Gm, l.ldq, ws + l.cd, stream);        // W^T W
+    if (rc) return rc;
+    rc = gpmp_coldots(Pi, n, q, ldpi, Pi, q, ldpi, ws + l.PtP, l.ldq, ws + l.cd, stream);
+    if (rc) return rc;
+    const size_t ms_bytes = sizeof(double) * (2 * QLD * (QLD + 1) + 3 * QLD);
+    GPMP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(meanspace_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)ms_bytes));
+    hipLaunchKernelGGL(meanspace_kernel, dim3(1), dim3(256), ms_bytes, st, ws + l.Gm, l.ldq, ws + l.PtP, l.ldq, q, n, ws + l.small,
+                       ws + l.Sinv, l.ldq, info_dev);
+    GPMP_HIP_TRY(hipGetLastError());
+  }
+  rc = gpmp_coldots(Kit, n, m, l.ldm, W, 1 + q, ldw, ws + l.D, l.ldm, ws + l.cd, stream);         // V^T [w, Wp] and colsumsq(V)
+  if (rc) return rc;
+  hipLaunchKernelGGL(pgrad_point_kernel, dim3((m + 255) / 256), dim3(256), 0, st, ws + l.D, l.ldm, Pt, ldpt, m, q, ws + l.Sinv, l.ldq,
+                     ws + l.small, sigma2, zero_neg_variances, info_dev, zpm_dev, zpv_dev, ws + l.vraw, ws + l.mu, l.ldm);
+  GPMP_HIP_TRY(hipGetLastError());
+  // mean weights K^-1 (z - P beta) = L^-T (w - Wp beta)
+  double* y = ws + l.y;
+  hipLaunchKernelGGL(pgrad_gamma_kernel, dim3((n + 255) / 256), dim3(256), 0, st, W, ldw, n, q, ws + l.small, y);
+  GPMP_HIP_TRY(hipGetLastError());
+  rc = gpmp_trsm_lower(K, n, l.ldn, dinv, y, 1, 1, 1, nullptr, stream);
+  if (rc) return rc;
+  const double* lam = nullptr;
+  if (with_variance_gradient) {
+    // kriging weights Lambda = L^-T (V - Wp mu), overwriting V (kriging.py:88-101 restated)
+    if (q > 0) {
+      rc = gpmp_dgemm(0, 0, n, m, q, -1.0, W + 1, ldw, ws + l.mu, l.ldm, 1.0, Kit, l.ldm, 0, stream);
+      if (rc) return rc;
+    }
+    rc = gpmp_trsm_lower(K, n, l.ldn, dinv, Kit, m, l.ldm, 1, nullptr, stream);
+    if (rc) return rc;
+    lam = Kit;
+  }
+  rc = gpmp_predict_grad_reduce(xi, xt, n, m, d, p, theta_host, noise, y, lam, l.ldm, gzpm_dev, with_variance_gradient ? gzpv_dev : nullptr,
+                                ws + l.red, stream);
+  if (rc) return rc;
+  const long md = (long)m * d;
+  hipLaunchKernelGGL(pgrad_finalize_kernel, dim3((unsigned)((md + 255) / 256)), dim3(256), 0, st, gzpm_dev,
+                     with_variance_gradient ? gzpv_dev : nullptr, J, m, d, q, ws + l.small, ws + l.mu, l.ldm, ws + l.vraw,
+                     zero_neg_variances, info_dev);
   GPMP_HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -335,6 +335,35 @@ int gpmp_predict_mean(const double* xi, const double* zi, const double* Pi, long
                       int zero_neg_variances, double* ws, double* zpm_dev, double* zpv_dev, int* info_dev,
                       gpmp_stream_t stream);
 
+/* ---- gradients of the prediction with respect to the prediction points ------------------------------------------
+ * The reference differentiates Model.predict by torch autograd (xt.requires_grad_()); here, with k(x, y) = sigma^2 K_p(h),
+ * h = || (x - y) / rho ||, S(h) = K_p'(h) / h (0 at h = 0 for every p) and
+ *   D[w]_{t,j} = sum_i w_it d k(x_i, x_t) / d x_tj = sigma^2 rho_j^-2 sum_i w_it S(h_it) (x_tj - x_ij):
+ *   d mean_t / d x_t = D[gamma]_t + beta^T J_t,   gamma = K^-1 (z - P beta),  beta = S^-1 P^T K^-1 z
+ *   d var_t / d x_t  = -2 D[lambda_t]_t - 2 mu_t^T J_t,   lambda_t / mu_t the kriging weights / Lagrange multipliers
+ * (q = 0: gamma = K^-1 z, lambda_t = K^-1 k_t, no J terms).
+ *
+ * gpmp_predict_grad_reduce: the fused pass alone.  gu (m x d, row-major) = D[u] with w_it = u_i (u: n values), gl (m x d) =
+ * D[Lambda] with w_it = Lambda[i * ldl + t] (n x m, ldl >= m); u / gu and Lambda / gl are given in pairs (either pair may be NULL,
+ * not both).  Covariance as gpmp_matern_gram (theta_host: [log sigma^2, (log noise variance,) log 1/rho_1 .. log 1/rho_d]);
+ * 0 <= p <= GPMP_MAX_P, 1 <= d <= GPMP_MAX_DIM_WIDE.  ws: gpmp_predict_grad_reduce_ws_elems(n, m, d) doubles.  Enqueue only. */
+size_t gpmp_predict_grad_reduce_ws_elems(int n, int m, int d);
+int gpmp_predict_grad_reduce(const double* xi, const double* xt, int n, int m, int d, int p, const double* theta_host, int noise,
+                             const double* u, const double* lam, long ldl, double* gu_dev, double* gl_dev, double* ws,
+                             gpmp_stream_t stream);
+
+/* Posterior mean and variance as gpmp_predict_mean (q >= 1) / gpmp_predict_zero_mean (q = 0: Pi, Pt and J may be NULL) plus
+ * their gradients with respect to xt: gzpm_dev, gzpv_dev (m x d, row-major).  J (m x q x d, J[(t q + a) d + j] =
+ * d Pt[t][a] / d xt[t][j]) is the Jacobian of the mean design at the prediction points.  with_variance_gradient = 0: only the
+ * mean gradient (no second n^2 m solve; gzpv_dev may then be NULL).  Where zero_neg_variances clamps a negative variance to 0,
+ * that row of gzpv is 0.  *info_dev as gpmp_predict_mean; when it is non-zero every output is NaN.
+ * ws: gpmp_predict_grad_ws_elems(n, m, d, q) doubles.  Enqueue only. */
+size_t gpmp_predict_grad_ws_elems(int n, int m, int d, int q);
+int gpmp_predict_grad(const double* xi, const double* zi, const double* Pi, long ldpi, const double* xt, const double* Pt,
+                      long ldpt, const double* J, int n, int m, int d, int q, int p, const double* theta_host, int noise,
+                      int zero_neg_variances, int with_variance_gradient, double* ws, double* zpm_dev, double* zpv_dev,
+                      double* gzpm_dev, double* gzpv_dev, int* info_dev, gpmp_stream_t stream);
+
 /* ---- many small problems at once (mini-batch criteria, posterior samplers) ------------------------------------- */
 
 /* B independent criteria -- the zero-mean NLL (q = 0) or REML with a mean design of q <= GPMP_BATCH_MAX_Q columns -- and, when
