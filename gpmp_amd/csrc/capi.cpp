@@ -30,6 +30,15 @@ int device_cu_count() {
   cache[dev].store(v, std::memory_order_relaxed);
   return v;
 }
+hipError_t stage_vector(std::vector<double>* v, double* dst, hipStream_t st) {
+  hipError_t e = hipMemcpyAsync(dst, v->data(), sizeof(double) * v->size(), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipLaunchHostFunc(st, [](void* q) { delete static_cast<std::vector<double>*>(q); }, v);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    delete v;
+  }
+  return e;
+}
 }  // namespace gpmp
 
 namespace gpmp {

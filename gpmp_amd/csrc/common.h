@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 #include <atomic>
+#include <vector>
 #include "../../include/gpmp_hip.h"
 
 namespace gpmp {
@@ -30,6 +31,10 @@ int hip_fail(hipError_t e, const char* what);
   } while (0)
 
 inline hipStream_t as_stream(gpmp_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// Copies *v to dst (device) behind the work already on st and frees v by a host function enqueued behind the copy, so the caller
+// stays enqueue-only.  Takes ownership of v in every case; on an error the stream has been synchronised and v freed (capi.cpp).
+hipError_t stage_vector(std::vector<double>* v, double* dst, hipStream_t st);
 
 // compute units of the CURRENT device (cached per device ordinal; 256 when the query fails): launch shapes that are fitted to the
 // machine (tile widths, strip widths, persistent grids) ask here, so a host thread per GPU sees its own device's count

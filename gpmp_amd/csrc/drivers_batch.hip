@@ -478,11 +478,7 @@ extern "C" int gpmp_nll_grad_batch(const double* x, long stride_x, const double*
       const double diag = noise ? std::exp(th[1]) : 10.0 * std::exp(th[0]) * DBL_EPSILON;      // matern.py:90
       fill_gram_param_block(blocks->data() + (size_t)pps * b, d, p, th, noise, diag);
     }
-    hipError_t ce = hipMemcpyAsync(ws + l.pp, blocks->data(), sizeof(double) * blocks->size(), hipMemcpyHostToDevice, st);
-    if (ce == hipSuccess) ce = hipLaunchHostFunc(st, [](void* v) { delete static_cast<std::vector<double>*>(v); }, blocks);
-    if (ce != hipSuccess) {
-      (void)hipStreamSynchronize(st);
-      delete blocks;
+    if (hipError_t ce = stage_vector(blocks, ws + l.pp, st)) {
       set_error("HIP error %s staging the per-problem parameters", hipGetErrorString(ce));
       return -100;
     }

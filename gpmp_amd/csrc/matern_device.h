@@ -1,9 +1,9 @@
-// Device helpers shared by the Gram / gradient kernels of gram.hip (d <= GPMP_MAX_DIM, parameters in the kernel arguments) and
-// gram_wide.hip (d up to GPMP_MAX_DIM_WIDE, length scales in device memory): the Matern polynomial, the fp64 sqrt / exp used on
-// the hot path, the tail of a Gram tile, and their host-side coefficient tables.  Everything is internal to the translation unit
-// that includes it.
+// Device helpers shared by the Gram / gradient kernels of gram.hip and the prediction-gradient kernels of predict_grad.hip: the
+// Matern polynomial, the fp64 sqrt / exp used on the hot path, and the host-side coefficient tables and parameter setup.
+// Everything is internal to the translation unit that includes it.
 #pragma once
 #include "common.h"
+#include <cfloat>
 #include <cmath>
 #include <vector>
 
@@ -97,89 +97,6 @@ __device__ __forceinline__ double matern_dk_over_h(const MaternSpec& ms, double 
   return (2.0 * ms.c) * (2.0 * ms.c) * e * s;
 }
 
-// The tail of one 128 x 64 Gram tile (gram_kernel_v3 and gram_wide_kernel): acc[a][b] holds the scaled squared distance of
-// this thread's entry (row0 + 8 ty + a, col0 + {2tx, 2tx+1, 32+2tx, 32+2tx+1}[b]); sqrt, then (MODE 0) the Matern polynomial
-// times exp(-t/2), the diagonal term on the diagonal, and the 16-byte stores.  Coefficients come in already loaded: qc[] for a
-// compile-time degree P, qk(k) for P < 0; qtop / c12 are the leading coefficients of the two Horner chains (held in VGPRs by
-// the caller).
-template <int P, int MODE, int NQ, class QK>
-__device__ __forceinline__ void gram_tile_finish(const double (&acc)[8][4], const FastExp fe, const double (&qc)[NQ], QK qk,
-                                                 double qtop, double c12, int pdeg, double dadd, bool diag_tile, bool full,
-                                                 double* __restrict__ out, long ldk, int row0, int col0, int ty, int tx, int pn,
-                                                 int pm) {
-#pragma unroll
-  for (int a = 0; a < 8; ++a, out += ldk) {
-    const int row = row0 + ty * 8 + a;
-    double v[4];
-    // the four entries of a row advance in lock step: every line below is four independent instructions, so one wave
-    // keeps the fp64 pipe fed across the ~26-deep dependent chain of an entry (measured with entry-after-entry code:
-    // 2.5 waves per SIMD resident, each waiting half of the time, VALU 60 % busy)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) v[b] = __builtin_amdgcn_rsq(acc[a][b] + fe.tiny);
-    double g[4], h[4], r[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) { g[b] = acc[a][b] * v[b]; h[b] = 0.5 * v[b]; }
-#pragma unroll
-    for (int b = 0; b < 4; ++b) r[b] = fma(-h[b], g[b], 0.5);
-#pragma unroll
-    for (int b = 0; b < 4; ++b) { g[b] = fma(g[b], r[b], g[b]); h[b] = fma(h[b], r[b], h[b]); }
-#pragma unroll
-    for (int b = 0; b < 4; ++b) r[b] = fma(-g[b], g[b], acc[a][b]);
-#pragma unroll
-    for (int b = 0; b < 4; ++b) g[b] = fma(r[b], h[b], g[b]);          // g = t = 2 c h (mode 0) or h (mode 1)
-    if constexpr (MODE == 0) {
-      double nk[4], e[4], poly[4];
-#pragma unroll
-      for (int b = 0; b < 4; ++b) nk[b] = rint(g[b] * fe.nl2e_half);   // -k
-#pragma unroll
-      for (int b = 0; b < 4; ++b) r[b] = fma(-nk[b], fe.ln2x2_hi, -g[b]);
-#pragma unroll
-      for (int b = 0; b < 4; ++b) r[b] = fma(-nk[b], fe.ln2x2_lo, r[b]);
-#pragma unroll
-      for (int b = 0; b < 4; ++b) { e[b] = c12; poly[b] = qtop; }
-      if constexpr (P >= 0) {
-#pragma unroll
-        for (int k = P - 1; k >= 0; --k)
-#pragma unroll
-          for (int b = 0; b < 4; ++b) poly[b] = fma(poly[b], g[b], qc[k]);
-      } else {
-        for (int k = pdeg - 1; k >= 0; --k) {
-          const double qkv = qk(k);
-#pragma unroll
-          for (int b = 0; b < 4; ++b) poly[b] = fma(poly[b], g[b], qkv);
-        }
-      }
-#pragma unroll
-      for (int j = 11; j >= 0; --j)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) e[b] = fma(e[b], r[b], fe.c[j]);
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const int k = (int)nk[b];                                        // saturating v_cvt_i32_f64
-        v[b] = ldexp(e[b], k < -1100 ? -1100 : k) * poly[b];             // exp underflows to 0 well before 2^-1100
-      }
-    } else {
-#pragma unroll
-      for (int b = 0; b < 4; ++b) v[b] = g[b];
-    }
-    if (diag_tile) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-        if (row == col0 + (b >> 1) * 32 + 2 * tx + (b & 1)) v[b] += dadd;
-    }
-    if (full) {
-      *reinterpret_cast<d2*>(out) = (d2){v[0], v[1]};
-      *reinterpret_cast<d2*>(out + 32) = (d2){v[2], v[3]};
-    } else if (row < pn) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const int cc = (b >> 1) * 32 + 2 * tx + (b & 1);
-        if (col0 + cc < pm) out[cc - 2 * tx] = v[b];
-      }
-    }
-  }
-}
-
 inline void fill_fast_exp(FastExp& fe) {
   fe.nl2e_half = -0.5 * 1.4426950408889634;
   fe.ln2x2_hi = 2.0 * 6.93147180369123816490e-01;
@@ -208,25 +125,40 @@ inline int fill_matern(MaternSpec& ms, int p) {
   return 0;
 }
 
+// Scale factors scale_k = factor exp(loginvrho_k) (factor 2 c: the variable t = 2 c h of the Matern polynomial; 1: plain 1 / rho_k).
+inline void fill_scales(double* out, const double* loginvrho, int d, double factor) {
+  for (int k = 0; k < d; ++k) out[k] = factor * std::exp(loginvrho[k]);
+}
+
+// The covariance parameters on the host, from theta = [log sigma^2, (log noise variance,) log(1 / rho_1) .. log(1 / rho_d)].
+struct MaternTheta {
+  MaternSpec ms;
+  int d, noise;
+  double sigma2;
+  double noise_var;              // 0 without a noise parameter
+  double nugget_scale;           // matern.py:90: without a noise parameter K gains 10 eps sigma2 I; this is 10 eps (else 0) ...
+  double nugget;                 // ... and this 10 sigma2 eps
+  const double* loginvrho;
+  MaternTheta(const double* theta, int noise_param, int p, int dim) : d(dim), noise(noise_param ? 1 : 0) {
+    fill_matern(ms, p);
+    sigma2 = std::exp(theta[0]);
+    noise_var = noise ? std::exp(theta[1]) : 0.0;
+    nugget_scale = noise ? 0.0 : 10.0 * DBL_EPSILON;
+    nugget = noise ? 0.0 : 10.0 * sigma2 * DBL_EPSILON;
+    loginvrho = theta + (noise ? 2 : 1);
+  }
+  // per-dimension factors: 2 c / rho_k (two_c) or 1 / rho_k
+  void scales(double* out, bool two_c) const { fill_scales(out, loginvrho, d, two_c ? 2.0 * ms.c : 1.0); }
+  std::vector<double>* scale_vector(bool two_c) const {
+    auto* v = new std::vector<double>((size_t)d);
+    scales(v->data(), two_c);
+    return v;
+  }
+  // sigma^2 q_k: K(h) = exp(-t/2) sum_k (sigma^2 q_k) t^k
+  void coefficients(double* q) const {
+    for (int k = 0; k <= GPMP_MAX_P; ++k) q[k] = sigma2 * ms.q[k];
+  }
+};
+
 }  // namespace
-
-// ---- the wide-dimension route (gram_wide.hip): GPMP_MAX_DIM < d <= GPMP_MAX_DIM_WIDE ----------------------------------------
-// The entry points of gram.hip check their arguments, compute the per-dimension factors on the host and hand them over here
-// (ownership of the vector passes to the callee, which stages it into device memory in stream order: every call only enqueues).
-//   gram_wide:       mode 0: K = Matern(t), t^2 = sum (scale_j (x_ij - y_kj))^2, scale_j = 2 c / rho_j, q = sigma^2 q_k; mode 1: the
-//                    scaled distance (scale_j = 1 / rho_j)
-//   pairwise_wide:   out[i] = sigma2 Matern(|| invrho (x_i - y_i) ||)
-//   gram_deriv_wide: gpmp_matern_gram_deriv (kind 0: d / d log sigma^2, 1: noise, 2: length scale jdim)
-//   grad_trace_wide: gpmp_matern_grad_trace (cross == 0) / gpmp_matern_grad_trace_cross; scale_j = 2 c / rho_j
-int gram_wide(const double* x, const double* y, int n, int m, int d, int mode, int p, std::vector<double>* scale, const double* q,
-              double diag_add, int lower_only, double* K, long ldk, hipStream_t st);
-int pairwise_wide(const double* x, const double* y, int n, int d, int p, double sigma2, std::vector<double>* invrho, double* out,
-                  hipStream_t st);
-int gram_deriv_wide(const double* x, int n, int d, int p, int kind, int jdim, double sigma2, double diag_val,
-                    std::vector<double>* invrho, double* out, long ld, hipStream_t st);
-int grad_trace_wide(const double* M, long ldm, const double* x, int n, const double* y, int m, int d, int p, double sigma2, int noise,
-                    double noise_var, std::vector<double>* scale, const double* F, const double* G, int r, long ldf, double* g_dev,
-                    double* ws, int cross, hipStream_t st);
-size_t grad_wide_ws_elems(int n, int d);
-
 }  // namespace gpmp

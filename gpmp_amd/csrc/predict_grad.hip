@@ -12,8 +12,6 @@
 // device memory, and the entries of a block of WIB observation points share each pass over the dimensions.  Slice 0 writes the
 // output array itself, slices s >= 1 a bounded partial buffer in the workspace; a finalize kernel sums the slices and scales.
 #include "matern_device.h"
-#include <cfloat>
-#include <vector>
 
 namespace gpmp {
 namespace {
@@ -246,23 +244,13 @@ extern "C" int gpmp_predict_grad_reduce(const double* xi, const double* xt, int 
   const PgLayout l = pg_layout(n, m, d);
   PgParams gp;
   std::memset(&gp, 0, sizeof(gp));
-  fill_matern(gp.ms, p);
+  const MaternTheta th(theta_host, noise, p, d);
+  gp.ms = th.ms;
   fill_fast_exp(gp.fe);
-  const double sigma2 = std::exp(theta_host[0]);
-  const int off = 1 + (noise ? 1 : 0);
-  auto* sv = new std::vector<double>((size_t)d);
-  for (int j = 0; j < d; ++j) (*sv)[j] = 2.0 * gp.ms.c * std::exp(theta_host[off + j]);
-  if (d <= GPMP_MAX_DIM)
-    for (int j = 0; j < d; ++j) gp.scale[j] = (*sv)[j];
-  // the factors in device memory (finalize, wide route): copied in stream order, the host vector freed behind the copy
+  if (d <= GPMP_MAX_DIM) th.scales(gp.scale, true);
+  // the factors in device memory (finalize, wide route)
   double* scale_dev = ws + l.scale;
-  hipError_t ce = hipMemcpyAsync(scale_dev, sv->data(), sizeof(double) * (size_t)d, hipMemcpyHostToDevice, st);
-  if (ce == hipSuccess) ce = hipLaunchHostFunc(st, [](void* q) { delete static_cast<std::vector<double>*>(q); }, sv);
-  if (ce != hipSuccess) {
-    (void)hipStreamSynchronize(st);
-    delete sv;
-    return hip_fail(ce, "staging the length scales");
-  }
+  if (hipError_t ce = stage_vector(th.scale_vector(true), scale_dev, st)) return hip_fail(ce, "staging the length scales");
   const int ns = pg_slices(n, m, d);
   gp.xi = xi;
   gp.xt = xt;
@@ -291,12 +279,12 @@ extern "C" int gpmp_predict_grad_reduce(const double* xi, const double* xt, int 
   const long md = (long)m * d;
   const unsigned fblocks = (unsigned)((md + 255) / 256);
   if (u != nullptr) {
-    hipLaunchKernelGGL(predict_grad_finalize_kernel, dim3(fblocks), dim3(256), 0, st, gu_dev, ws + l.part, ns - 1, md, d, scale_dev, sigma2);
+    hipLaunchKernelGGL(predict_grad_finalize_kernel, dim3(fblocks), dim3(256), 0, st, gu_dev, ws + l.part, ns - 1, md, d, scale_dev, th.sigma2);
     GPMP_HIP_TRY(hipGetLastError());
   }
   if (lam != nullptr) {
     hipLaunchKernelGGL(predict_grad_finalize_kernel, dim3(fblocks), dim3(256), 0, st, gl_dev, ws + l.part + l.part_kind, ns - 1, md, d,
-                       scale_dev, sigma2);
+                       scale_dev, th.sigma2);
     GPMP_HIP_TRY(hipGetLastError());
   }
   return 0;

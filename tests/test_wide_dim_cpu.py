@@ -78,9 +78,9 @@ def test_grad_workspace_grows_with_d_above_64(lib):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_wide_kernels_use_no_scratch_and_no_spills():
+def test_wide_instances_in_gram_hip_use_no_scratch_and_no_spills():
     cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-mllvm", "-amdgpu-mfma-vgpr-form=1",
-           "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, "gram_wide.hip"), "-o", os.devnull]
+           "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, "gram.hip"), "-o", os.devnull]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     res, name = {}, None
@@ -93,16 +93,16 @@ def test_wide_kernels_use_no_scratch_and_no_spills():
         m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
         if m and name:
             res[name][m.group(1).strip()] = int(m.group(2))
-    for frag in ("gram_wide_kernel", "grad_trace_wide_kernel", "pairwise_wide_kernel", "gram_deriv_wide_kernel",
+    for frag in ("gram_kernel_v3", "GramWideParams", "grad_trace_wide_kernel", "PairWideParams", "DerivWideParams",
                  "grad_wide_finalize_kernel"):
         hit = {k: v for k, v in res.items() if frag in k}
         assert hit, (frag, sorted(res))
         for k, v in hit.items():
             assert v.get("ScratchSize", 0) == 0, (k, v)
             assert v.get("VGPRs Spill", 0) == 0, (k, v)
-    # the Gram tile keeps gram_kernel_v3's register budget (two workgroups per CU)
+    # every instance of the Gram tile, wide or not, keeps the register budget of two workgroups per CU
     for k, v in res.items():
-        if "gram_wide_kernel" in k:
+        if "gram_kernel_v3" in k:
             assert v["VGPRs"] <= 128, (k, v)
 
 

@@ -1,5 +1,5 @@
 """Inputs of dimension d > GPMP_MAX_DIM (= 64) through every path that builds a covariance: the wide-dimension kernels
-(gpmp_amd/csrc/gram_wide.hip) behind gpmp_matern_gram, gpmp_scaled_distance, gpmp_matern_pairwise, gpmp_matern_gram_deriv,
+(the wide route of gpmp_amd/csrc/gram.hip) behind gpmp_matern_gram, gpmp_scaled_distance, gpmp_matern_pairwise, gpmp_matern_gram_deriv,
 gpmp_matern_grad_trace(_cross) and the fused drivers, checked against the reference's own outputs (tests/golden/ref_wide_dim.npz,
 written by make_fixtures_wide_dim.py) and the CPU oracle.
 
