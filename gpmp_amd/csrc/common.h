@@ -32,6 +32,14 @@ int hip_fail(hipError_t e, const char* what);
 
 inline hipStream_t as_stream(gpmp_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+inline long pad16(long v) { return (v + 15) / 16 * 16; }
+
+// Cursor over a caller-owned workspace of doubles: every slot starts on a multiple of 16 elements; `at` ends up as the total.
+struct WsCursor {
+  size_t at = 0;
+  size_t take(size_t count) { const size_t o = at; at += (size_t)pad16((long)count); return o; }
+};
+
 // Copies *v to dst (device) behind the work already on st and frees v by a host function enqueued behind the copy, so the caller
 // stays enqueue-only.  Takes ownership of v in every case; on an error the stream has been synchronised and v freed (capi.cpp).
 hipError_t stage_vector(std::vector<double>* v, double* dst, hipStream_t st);

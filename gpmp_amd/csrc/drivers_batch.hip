@@ -26,7 +26,6 @@ constexpr int BQ = 16;             // mean-design columns supported in the batch
 constexpr int BR = BQ + 1;         // right-hand sides per problem: [z, P]; the kernels exist for 4 (q <= 3), 8 (q <= 7) and 17 of them
 constexpr int BSM = 288;           // doubles of per-problem scalars: [0] logdet K, [1] quad, [2] ln|S|, [3] ln|PtP|, [4] fail,
                                    // [8 + a] c = S^-1 b, [24 + BQ a + b] S^-1
-inline long pad16(long v) { return (v + 15) / 16 * 16; }
 
 // identity in the padding of one slot: rows / columns n .. nmax - 1 (lower triangle + diagonal are what the factorisation reads)
 __global__ void pad_identity_kernel(double* __restrict__ K, long ld, int n, int nmax) {
@@ -374,20 +373,19 @@ BatchLayout batch_layout(int nmax, int d, int q, int B, bool grad) {
   l.sD = (size_t)pad16((long)((nmax + NB - 1) / NB) * NB * NB);
   l.sY = (size_t)nmax * l.ldq;
   l.sG = (size_t)pad16((long)gpmp_grad_ws_elems(nmax, d));
-  size_t o = 0;
-  auto take = [&](size_t cnt) { size_t at = o; o += (size_t)pad16((long)cnt); return at; };
-  l.K = take(l.sK * B);
-  l.dinv = take(l.sD * B);
-  l.T = grad ? take(l.sK * B) : 0;
-  l.Y = take(l.sY * B);
-  l.X = grad ? take(l.sY * B) : 0;
-  l.F = grad ? take(l.sY * B) : 0;
-  l.G = grad ? take(l.sY * B) : 0;
-  l.small = take((size_t)BSM * B);
-  l.ns = take((size_t)(B + 1) / 2 + 8);     // B ints
-  l.gws = grad ? take(l.sG * B) : 0;
-  l.pp = take((size_t)gram_param_block_elems() * B);      // per-problem parameter blocks (sampler pattern)
-  l.total = o;
+  WsCursor c;
+  l.K = c.take(l.sK * B);
+  l.dinv = c.take(l.sD * B);
+  l.T = grad ? c.take(l.sK * B) : 0;
+  l.Y = c.take(l.sY * B);
+  l.X = grad ? c.take(l.sY * B) : 0;
+  l.F = grad ? c.take(l.sY * B) : 0;
+  l.G = grad ? c.take(l.sY * B) : 0;
+  l.small = c.take((size_t)BSM * B);
+  l.ns = c.take((size_t)(B + 1) / 2 + 8);     // B ints
+  l.gws = grad ? c.take(l.sG * B) : 0;
+  l.pp = c.take((size_t)gram_param_block_elems() * B);      // per-problem parameter blocks (sampler pattern)
+  l.total = c.at;
   return l;
 }
 

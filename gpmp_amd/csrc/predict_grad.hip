@@ -22,8 +22,6 @@ constexpr int PG_MIN_ROWS = 64;           // observation points per slice, at le
 constexpr long PG_PART_CAP = 1L << 22;    // doubles of partials per weight kind (32 MB)
 constexpr int WIB = 8;                    // wide route: observation points per pass over the dimensions
 
-inline long pad16(long v) { return (v + 15) / 16 * 16; }
-
 struct PgParams {
   const double* xi;
   const double* xt;
