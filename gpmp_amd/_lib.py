@@ -35,6 +35,10 @@ SIGNATURES = {
     "gpmp_dinv_elems": (c_size_t, [c_int]),
     "gpmp_potrf_lower_async": (c_int, [_P, c_int, c_long, _P, _P, _P]),
     "gpmp_potrf_trsm_lower_async": (c_int, [_P, c_int, c_long, _P, _P, _P, c_int, c_long, _P]),
+    "gpmp_strassen_ws_elems": (c_size_t, [c_int, c_int]),
+    "gpmp_set_strassen_thresholds": (None, [c_int, c_int]),
+    "gpmp_debug_strassen_ws_elems": (c_size_t, [c_int, c_int]),
+    "gpmp_debug_strassen_update": (c_int, [_P, c_long, _P, c_long, _P, c_long, c_int, c_int, _P, c_size_t, _P]),
     "gpmp_trsm_lower": (c_int, [_P, c_int, c_long, _P, _P, c_int, c_long, c_int, _P, _P]),
     "gpmp_solve_status": (c_int, [_P, _P]),
     "gpmp_trsm_right_lower": (c_int, [_P, c_int, c_long, _P, _P, c_int, c_long, _P]),

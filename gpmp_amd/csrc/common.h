@@ -107,6 +107,11 @@ struct GemmOpts {
   // / kg_cden)) -- what lies before is structurally zero in both operands' block columns.  den > 0 enables the respective term; tiles
   // of unequal cost are dealt round-robin over the XCDs.  Combines with the staircase tile set, with nothing else.
   int kg_rnum = 0, kg_rden = 0, kg_roff = 0, kg_cnum = 0, kg_cden = 0, kg_coff = 0;
+  // Second destination (NN kind, beta == 1, nothing else of the above): C += sign1 alpha A B and c2 += sign2 alpha A B from ONE
+  // product -- the products of a Strassen step go straight into the one or two quadrants that take them (linalg.hip).
+  double* c2 = nullptr;
+  long ldc2 = 0;
+  double sign1 = 1.0, sign2 = 1.0;
 };
 int launch_gemm(bool a_kc, bool b_kc, int M, int N, int K, double alpha, const double* A, long lda,
                 const double* B, long ldb, double beta, double* C, long ldc, const GemmOpts& o,
@@ -136,6 +141,15 @@ int launch_tril(double* A, int n, long lda, hipStream_t st, int nprob = 1, long 
 int launch_symmetrize(double* A, int n, long lda, hipStream_t st);
 int launch_diag_blocks(double* T, int n, long ldt, const double* dinv, hipStream_t st, int nprob = 1, long prob_stride_t = 0,
                        long prob_stride_dinv = 0);
+// D = X + sign Y (rows x cols, cols even, every operand 16-byte aligned with an even leading dimension)
+int launch_block_sum(const double* X, long ldx, const double* Y, long ldy, double sign, double* D, long ldd, int rows, int cols,
+                     hipStream_t st);
+
+// ---- factorisation + forward solve with the Strassen scratch of the solve's large updates (linalg.hip) -----------------------
+// gpmp_potrf_trsm_lower_async with `sws` (gpmp_strassen_ws_elems(n, m) doubles, or NULL: plain recursion): the fused drivers carve
+// it from their workspace.  sws_elems is what the caller reserved; less than the solve needs is an argument error.
+int potrf_trsm_lower_ws(double* A, int n, long lda, double* dinv, int* info_dev, double* B, int m, long ldb, double* sws,
+                        size_t sws_elems, hipStream_t st);
 
 // ---- batched small problems (linalg.hip): `nprob` independent n x n matrices (n <= GPMP_BATCH_MAX_N), a fixed number of
 // elements apart; every step is ONE launch over all problems (blockIdx.y / .z = problem)

@@ -319,7 +319,7 @@ enum : unsigned {
 };
 struct DriverLayout {
   long ldn, ldm, ldq;
-  size_t K, dinv, T, W, X, F, G, Kit, Gm, PtP, Sinv, small, scal, D, dcol, cd, y, vraw, mu, red, gws, total;
+  size_t K, dinv, T, W, X, F, G, Kit, Gm, PtP, Sinv, small, scal, D, dcol, cd, y, vraw, mu, red, gws, sws, sws_elems, total;
 };
 // m = 0 for the drivers without prediction points
 DriverLayout driver_layout(int n, int m, int d, int q, unsigned use) {
@@ -354,6 +354,12 @@ DriverLayout driver_layout(int n, int m, int d, int q, unsigned use) {
     l.red = c.take(gpmp_predict_grad_reduce_ws_elems(n, m, d));
   }
   if (use & WS_FG) l.gws = c.take(gpmp_grad_ws_elems(n, d));
+  // last, so that every other slot stays where it was: the Strassen scratch of the prediction solve's large updates (nothing below
+  // the thresholds, see gpmp_strassen_ws_elems), sized for the solve's m + 1 + q columns rounded up to even
+  if (use & WS_KIT) {
+    l.sws_elems = gpmp_strassen_ws_elems(n, (m + 1 + q) + ((m + 1 + q) & 1));
+    l.sws = c.take(l.sws_elems);
+  }
   l.total = c.at;
   return l;
 }
@@ -475,7 +481,7 @@ int predict_solve(const Cov& cov, const DriverLayout& l, const double* xi, const
   if (rc) return rc;
   const int mb = (m + 1 + q) + ((m + 1 + q) & 1);
   if (mb > m + 1 + q) GPMP_HIP_TRY(hipMemset2DAsync(Kit + m + 1 + q, (size_t)l.ldm * sizeof(double), 0, sizeof(double), n, st));
-  return gpmp_potrf_trsm_lower_async(K, n, l.ldn, ws + l.dinv, info_dev, Kit, mb, l.ldm, stream);
+  return potrf_trsm_lower_ws(K, n, l.ldn, ws + l.dinv, info_dev, Kit, mb, l.ldm, l.sws_elems ? ws + l.sws : nullptr, l.sws_elems, st);
 }
 }  // namespace
 }  // namespace gpmp

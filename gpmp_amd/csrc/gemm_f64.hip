@@ -52,6 +52,10 @@ struct GemmParams {
   int kg_rnum, kg_rden, kg_roff, kg_cnum, kg_cden, kg_coff;   // contraction start per group of 8 tile rows / columns (GemmOpts)
   long sa, sb, sc;   // element strides of A, B, C per batch index
   long sa2, sb2, sc2;   // ... per outer batch index (blockIdx.z)
+  // two-destination accumulate (gemm_f64_kernel_v2<..., DUAL = true> only): C += sign1 alpha A B and C2 += sign2 alpha A B
+  double* C2;
+  long ldc2;
+  double sign1, sign2;
 };
 
 // tile columns of the group g of 8 tile rows of a staircase tile set (host and device)
@@ -442,8 +446,12 @@ __device__ __forceinline__ int v2_frag_addr(int idx, int k) {
 // leaves).  Narrower tiles exist for ONE reason: a launch lasts ceil(tiles / (2 CUs)) rounds of the machine, and with N = 50000
 // (391 tile columns of 128) the solve's updates of 512 ... 4096 rows end on a nearly empty round -- 447 columns of 112 fit better
 // (launch_t picks the width that minimises rounds x width).  Everything else -- operand images, request schedule, k loop -- is shared.
-template <bool AKC, bool BKC, bool CACC, int BNT = BN>
+// DUAL (the Strassen update of the forward solve, linalg.hip): the accumulators start from zero and the epilogue ADDS the product
+// to two destinations, C += sign1 alpha P and C2 += sign2 alpha P, as read-modify-write of the tile with the 16-byte accesses of the
+// pure-store epilogue.  Everything before the epilogue is shared; the single-destination instances do not see any of it.
+template <bool AKC, bool BKC, bool CACC, int BNT = BN, bool DUAL = false>
 __global__ void __launch_bounds__(256, 2) gemm_f64_kernel_v2(GemmParams p) {
+  static_assert(!DUAL || !CACC, "the two-destination epilogue starts from zero accumulators");
   constexpr int MI = BNT == BN ? 4 : 2;            // 16-row MFMA tiles per wave
   constexpr int NJ = BNT == BN ? 4 : BNT / 16;     // 16-column MFMA tiles per wave
   extern __shared__ __attribute__((aligned(16))) double smem[];  // [2 buffers][A image | B image] = 64 KB
@@ -655,6 +663,57 @@ __global__ void __launch_bounds__(256, 2) gemm_f64_kernel_v2(GemmParams p) {
     for (; kt < nk; ++kt) ktile(kt, kt + 1 < nk, nothing);
   }
 
+  if constexpr (DUAL) {
+    double* __restrict__ cbase2 = p.C2 + (long)row0 * p.ldc2 + col0;
+    const double s1 = p.sign1 * alpha, s2 = p.sign2 * alpha;
+    const unsigned lane_off2 = (unsigned)((wm + lk) * (int)p.ldc2 + wn + lr);
+    if (!edge) {
+      // the lane pairing of the pure-store epilogue below: the even lane owns rows r = 0, 1 of a column pair, the odd lane rows 2, 3
+      const bool odd = lane & 1;
+      const unsigned o1 = lane_off - (odd ? 1u : 0u), o2 = lane_off2 - (odd ? 1u : 0u);
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        double* r1 = cbase + (long)(i * 16 + (odd ? 8 : 0)) * p.ldc + o1;
+        double* r2 = cbase2 + (long)(i * 16 + (odd ? 8 : 0)) * p.ldc2 + o2;
+        d2 c1[NJ][2], c2[NJ][2];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          c1[j][0] = *reinterpret_cast<const d2*>(r1 + j * 16);
+          c1[j][1] = *reinterpret_cast<const d2*>(r1 + 4 * p.ldc + j * 16);
+          c2[j][0] = *reinterpret_cast<const d2*>(r2 + j * 16);
+          c2[j][1] = *reinterpret_cast<const d2*>(r2 + 4 * p.ldc2 + j * 16);
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const double a0 = acc[i][j][0], a1 = acc[i][j][1], a2 = acc[i][j][2], a3 = acc[i][j][3];
+          const double g0 = swap_lane_xor1(odd ? a0 : a2), g1 = swap_lane_xor1(odd ? a1 : a3);
+          const d2 v0 = odd ? (d2){g0, a2} : (d2){a0, g0};
+          const d2 v1 = odd ? (d2){g1, a3} : (d2){a1, g1};
+          *reinterpret_cast<d2*>(r1 + j * 16) = c1[j][0] + s1 * v0;
+          *reinterpret_cast<d2*>(r1 + 4 * p.ldc + j * 16) = c1[j][1] + s1 * v1;
+          *reinterpret_cast<d2*>(r2 + j * 16) = c2[j][0] + s2 * v0;
+          *reinterpret_cast<d2*>(r2 + 4 * p.ldc2 + j * 16) = c2[j][1] + s2 * v1;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          double* rp = cbase + (long)(i * 16 + 4 * r) * p.ldc;
+          double* rq = cbase2 + (long)(i * 16 + 4 * r) * p.ldc2;
+          const bool rok = wm + i * 16 + 4 * r + lk < rows_v;
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) {
+            if (rok && wn + j * 16 + lr < cols_v) {
+              rp[lane_off + j * 16] += s1 * acc[i][j][r];
+              rq[lane_off2 + j * 16] += s2 * acc[i][j][r];
+            }
+          }
+        }
+    }
+    return;
+  }
   if (!edge && (CACC || beta == 0.0)) {
     // Pure store of a full tile with 16-byte stores: in the MFMA layout a lane holds ONE column of four rows (4 apart), so
     // neighbouring lanes (columns c, c + 1) swap half of their registers (DPP quad_perm [1,0,3,2]): the even lane then owns
@@ -1178,6 +1237,52 @@ int launch_t(const GemmParams& p, hipStream_t st) {
   return 0;
 }
 
+// Two destinations (GemmOpts::c2): NN kind on the LDS-direct kernel, 128-column tiles.  There is no other kernel for it: a product
+// the LDS-direct kernel cannot take is an error.
+int launch_dual(const GemmParams& p, hipStream_t st) {
+  static DeviceOnce attr_once;
+  const size_t lds2 = sizeof(double) * 4 * V2_TILE;
+  if (const long long dev_bit = attr_once.need()) {
+    if (dev_bit < 0) { set_error("hipGetDevice failed or device ordinal above 62"); return -1; }
+    GPMP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_v2<true, false, false, BN, true>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+    GPMP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_v2<true, false, false, 112, true>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+    GPMP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_v2<true, false, false, 96, true>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+    attr_once.done(dev_bit);
+  }
+  const bool ok = p.aligned && (p.M % 2 == 0) && (p.N % 2 == 0) && (p.K % BK == 0) && p.K > 0 && p.alpha != 0.0 && p.beta == 1.0 &&
+                  ((reinterpret_cast<uintptr_t>(p.C) & 15) == 0) && (p.ldc % 2 == 0) && (p.ldc >= p.N) &&
+                  ((reinterpret_cast<uintptr_t>(p.C2) & 15) == 0) && (p.ldc2 % 2 == 0) && (p.ldc2 >= p.N) &&
+                  ((long)BM * p.lda * 8 + (long)p.K * 8 < 0x7FFFFFFFL) && ((long)BN * p.ldb * 8 + (long)p.K * 8 < 0x7FFFFFFFL) &&
+                  ((long)BM * p.ldc * 8 < 0x7FFFFFFFL) && ((long)BM * p.ldc2 * 8 < 0x7FFFFFFFL) &&
+                  p.batch == 1 && p.batch2 == 1 && !p.lower_only && !p.stair_den &&
+                  !(p.kstart_row | p.kend_row | p.kstart_col | p.kend_col | p.kg_rden | p.kg_cden);
+  if (!ok) { set_error("two-destination product: operands not 16-byte aligned, odd sizes, K not a multiple of 16, beta != 1 or a restricted tile set"); return -1; }
+  // tile width as for a plain launch (launch_t): the width among 128 / 112 / 96 that minimises rounds x width
+  GemmParams pf = p;
+  if (p.N >= 16 * BN) {
+    const long slots = 2L * device_cu_count();
+    auto cost = [&](int w) { const long t = (long)p.tiles_m * ((p.N + w - 1) / w); return ((t + slots - 1) / slots) * (long)w; };
+    long best = cost(BN);
+    for (int w : {112, 96}) {
+      const long c = cost(w);
+      if (c * 100 < best * 97) { best = c; pf.bn = w; }
+    }
+    pf.tiles_n = (p.N + pf.bn - 1) / pf.bn;
+    pf.ntiles = pf.tiles_m * pf.tiles_n;
+  }
+  {
+    ProfScope ps(PK_GEMM2_NN, st, 2.0 * (double)p.M * (double)p.N * (double)p.K);
+    if (pf.bn == 112) hipLaunchKernelGGL((gemm_f64_kernel_v2<true, false, false, 112, true>), dim3(pf.ntiles), dim3(256), lds2, st, pf);
+    else if (pf.bn == 96) hipLaunchKernelGGL((gemm_f64_kernel_v2<true, false, false, 96, true>), dim3(pf.ntiles), dim3(256), lds2, st, pf);
+    else hipLaunchKernelGGL((gemm_f64_kernel_v2<true, false, false, BN, true>), dim3(pf.ntiles), dim3(256), lds2, st, pf);
+  }
+  GPMP_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 template <bool AKC, bool BKC>
 int launch_c(const GemmParams& p, hipStream_t st) {
   if (p.beta != 0.0 && p.alpha != 0.0) return launch_t<AKC, BKC, true>(p, st);
@@ -1303,6 +1408,11 @@ static int launch_gemm_one(bool a_kc, bool b_kc, int M, int N, int K, double alp
   p.sa2 = o.stride2_a; p.sb2 = o.stride2_b; p.sc2 = o.stride2_c;
   p.aligned = ((reinterpret_cast<uintptr_t>(A) & 15) == 0) && ((lda & 1) == 0) &&
               ((reinterpret_cast<uintptr_t>(B) & 15) == 0) && ((ldb & 1) == 0);
+  p.C2 = o.c2; p.ldc2 = o.ldc2; p.sign1 = o.sign1; p.sign2 = o.sign2;
+  if (o.c2 != nullptr) {
+    if (!(a_kc && !b_kc)) { set_error("two-destination product: NN kind only"); return -1; }
+    return launch_dual(p, st);
+  }
   if (a_kc && b_kc) return launch_c<true, true>(p, st);
   if (a_kc && !b_kc) return launch_c<true, false>(p, st);
   if (!a_kc && !b_kc) return launch_c<false, false>(p, st);
@@ -1315,7 +1425,7 @@ int launch_gemm(bool a_kc, bool b_kc, int M, int N, int K, double alpha, const d
   if (M <= 0 || N <= 0) return 0;
   // The LDS-direct kernel needs even M and N (16-byte clipping at the edges): peel an odd last row / column off a
   // large rectangular product so that everything else runs on it.
-  const bool plain = !o.lower_only && !o.stair_den && !o.kg_rden && !o.kg_cden && !o.kstart_row && !o.kend_row && !o.kstart_col && !o.kend_col && o.batch <= 1 && o.batch2 <= 1;
+  const bool plain = !o.lower_only && !o.stair_den && !o.kg_rden && !o.kg_cden && !o.kstart_row && !o.kend_row && !o.kstart_col && !o.kend_col && o.batch <= 1 && o.batch2 <= 1 && o.c2 == nullptr;
   const int Nr = N % 2, Mr = M % 2;
   if (plain && (Nr || Mr) && (K % BK == 0) && K >= 512 && (M >= 4 * BM || N >= 4 * BN) && C != A && C != B) {
     const int Mf = M - Mr, Nf = N - Nr;

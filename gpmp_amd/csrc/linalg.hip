@@ -301,7 +301,9 @@ int factor_panel(double* A, int n, long lda, double* dinv, int* info_dev, int p0
   return need_cols(p1 + 1);                    // (every piece is waited for: the panel event stands for the whole panel)
 }
 
-int trsm_forward(const double* L, int n, long ldl, const double* dinv, double* B, int m, long ldb, double* gws, hipStream_t st);
+struct StrassenWs;
+int trsm_forward(const double* L, int n, long ldl, const double* dinv, double* B, int m, long ldb, double* gws, hipStream_t st,
+                 const StrassenWs* sw = nullptr);
 
 // Solve along (chain-bound sizes, n <= 8192: the factorisation leaves most of the machine idle): B (n x m) <- L^-1 B with the rows
 // of every piece of panels solved as soon as those panels are factored, on a third stream -- a block solve
@@ -499,8 +501,98 @@ int potrf_lower(double* A, int n, long lda, double* dinv, int* info_dev, hipStre
   return potrf_lookahead(A, n, lda, dinv, info_dev, st);
 }
 
+// ---- one Strassen level in the large updates of the forward solve ----------------------------------------------------------------
+// The update B2 -= L21 X1 of a recursion node (L21: M x K, X1: K x N) is 2 M K N flop on a kernel that runs at 0.93 of the matrix
+// peak: the only thing left to cut is the flop count.  With every operand in quadrants (rows M / 2, K / 2; columns split at Nh, the
+// largest multiple of 128 not above N / 2, so that quadrants are whole tiles; the N - 2 Nh columns left over take the plain product)
+// the classic seven products replace the eight, and each goes through the two-destination GEMM straight into the one or two
+// quadrants of B2 that take it -- no pass over B2 besides the products' own epilogues:
+//   M1 = (A11 + A22)(B11 + B22) -> C11, C22     M2 = (A21 + A22) B11 -> C21, -C22     M3 = A11 (B12 - B22) -> C12, C22
+//   M4 = A22 (B21 - B11) -> C11, C21            M5 = (A11 + A12) B22 -> -C11, C12     M6 = (A21 - A11)(B11 + B12) -> C22
+//   M7 = (A12 - A22)(B21 + B22) -> C11          (all times alpha = -1: the update subtracts)
+// The operand sums go through ONE left scratch block (M / 2 x K / 2) and ONE right scratch block (K / 2 x Nh), reused product
+// after product: everything is enqueued on the caller's stream in program order, so the reuse needs no event.
+// Thresholds (process-wide, gpmp_set_strassen_thresholds; the constants are the defaults):
+//   STRASSEN_MIN_ROWS: K of the update.  8192 takes the top update and the two below it at n = 32768 (3/4 of the solve's flops).
+//     A/B in one process, prediction at n = 32768, m = 50000 (profiles/r6/strassen_threshold_sweep.log, median ms): plain 934.4,
+//     16384 rows 903.5, 8192 rows 892.7, 4096 rows 892.65 (neutral -- and it would take n = 8192 off the solve-along route),
+//     2048 rows 900.5.
+//   STRASSEN_MIN_COLS: below 16384 columns the half-size products of an 8192-row update (32 tile rows x N / 256 tile columns) are
+//     fewer than four rounds of the machine's 512 workgroup slots and the ragged last round costs what the seventh product saves.
+constexpr int STRASSEN_MIN_ROWS = 8192;
+constexpr int STRASSEN_MIN_COLS = 16384;
+std::mutex g_strassen_mu;
+int g_strassen_min_rows = STRASSEN_MIN_ROWS, g_strassen_min_cols = STRASSEN_MIN_COLS;
+struct StrassenLimits { int rows, cols; };
+StrassenLimits strassen_limits() {
+  std::lock_guard<std::mutex> lk(g_strassen_mu);
+  return {g_strassen_min_rows, g_strassen_min_cols};
+}
+struct StrassenWs {
+  double* p = nullptr;
+  size_t elems = 0;
+  StrassenLimits lim = {STRASSEN_MIN_ROWS, STRASSEN_MIN_COLS};
+};
+
+inline int strassen_col_split(int N) { return (N / 2) / NB * NB; }
+// shapes the step takes: whole-tile quadrants, an even number of columns left over
+inline bool strassen_shape_ok(int M, int K, int N) {
+  return M > 0 && K > 0 && M % (2 * NB) == 0 && K % (2 * NB) == 0 && N % 2 == 0 && strassen_col_split(N) >= NB;
+}
+inline size_t strassen_node_elems(int M, int K, int N) {
+  return (size_t)pad16((long)(M / 2) * (K / 2)) + (size_t)pad16((long)(K / 2) * strassen_col_split(N));
+}
+// scratch of the forward solve of n rows and m columns: the largest node of trsm_forward's recursion that takes the step
+size_t strassen_solve_elems(int n, int m, const StrassenLimits& lim) {
+  if (n <= LEAF_TRSM) return 0;
+  const int n1 = split_point(n);
+  size_t need = (n1 >= lim.rows && m >= lim.cols && strassen_shape_ok(n - n1, n1, m)) ? strassen_node_elems(n - n1, n1, m) : 0;
+  const size_t a = strassen_solve_elems(n1, m, lim), b = strassen_solve_elems(n - n1, m, lim);
+  if (a > need) need = a;
+  if (b > need) need = b;
+  return need;
+}
+
+// C (M x N) -= A (M x K) B (K x N), strassen_shape_ok(M, K, N), every operand 16-byte aligned with an even leading dimension;
+// ws: strassen_node_elems(M, K, N) doubles
+int strassen_update(const double* A, long lda, const double* B, long ldb, double* C, long ldc, int M, int K, int N, double* ws,
+                    hipStream_t st) {
+  const int Mh = M / 2, Kh = K / 2, Nh = strassen_col_split(N), Np = N - 2 * Nh;
+  const double *A11 = A, *A12 = A + Kh, *A21 = A + (long)Mh * lda, *A22 = A21 + Kh;
+  const double *B11 = B, *B12 = B + Nh, *B21 = B + (long)Kh * ldb, *B22 = B21 + Nh;
+  double *C11 = C, *C12 = C + Nh, *C21 = C + (long)Mh * ldc, *C22 = C21 + Nh;
+  double* S = ws;                                        // Mh x Kh, ld Kh
+  double* T = ws + pad16((long)Mh * Kh);                 // Kh x Nh, ld Nh
+  auto lsum = [&](const double* X, const double* Y, double sign) { return launch_block_sum(X, lda, Y, lda, sign, S, Kh, Mh, Kh, st); };
+  auto rsum = [&](const double* X, const double* Y, double sign) { return launch_block_sum(X, ldb, Y, ldb, sign, T, Nh, Kh, Nh, st); };
+  auto prod = [&](const double* Ao, long ldao, const double* Bo, long ldbo, double* Ca, double sa, double* Cb, double sb) {
+    GemmOpts o;
+    o.c2 = Cb; o.ldc2 = ldc; o.sign1 = sa; o.sign2 = sb;
+    return launch_gemm(true, false, Mh, Nh, Kh, -1.0, Ao, ldao, Bo, ldbo, 1.0, Ca, ldc, o, st);
+  };
+  int rc;
+  if ((rc = lsum(A11, A22, 1.0)) || (rc = rsum(B11, B22, 1.0)) || (rc = prod(S, Kh, T, Nh, C11, 1.0, C22, 1.0))) return rc;      // M1
+  if ((rc = lsum(A21, A22, 1.0)) || (rc = prod(S, Kh, B11, ldb, C21, 1.0, C22, -1.0))) return rc;                                // M2
+  if ((rc = rsum(B12, B22, -1.0)) || (rc = prod(A11, lda, T, Nh, C12, 1.0, C22, 1.0))) return rc;                                // M3
+  if ((rc = rsum(B21, B11, -1.0)) || (rc = prod(A22, lda, T, Nh, C11, 1.0, C21, 1.0))) return rc;                                // M4
+  if ((rc = lsum(A11, A12, 1.0)) || (rc = prod(S, Kh, B22, ldb, C11, -1.0, C12, 1.0))) return rc;                                // M5
+  if ((rc = lsum(A21, A11, -1.0)) || (rc = rsum(B11, B12, 1.0)) || (rc = prod(S, Kh, T, Nh, C22, 1.0, nullptr, 0.0))) return rc; // M6
+  if ((rc = lsum(A12, A22, -1.0)) || (rc = rsum(B21, B22, 1.0)) || (rc = prod(S, Kh, T, Nh, C11, 1.0, nullptr, 0.0))) return rc; // M7
+  if (Np > 0) {
+    GemmOpts plain;
+    rc = launch_gemm(true, false, M, Np, K, -1.0, A, lda, B + 2 * Nh, ldb, 1.0, C + 2 * Nh, ldc, plain, st);
+  }
+  return rc;
+}
+
+inline bool strassen_operands_ok(const double* A, long lda, const double* B, long ldb) {
+  return ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 && lda % 2 == 0 && ldb % 2 == 0;
+}
+
 // gws: optional scratch of at least (LEAF_TRSM)^2 doubles; enables the fused leaf (gemm_f64.hip: trsm_leaf_kernel)
-int trsm_forward(const double* L, int n, long ldl, const double* dinv, double* B, int m, long ldb, double* gws, hipStream_t st) {
+// sw: optional scratch of the Strassen step (strassen_solve_elems): updates at or above its thresholds take it
+int trsm_forward(const double* L, int n, long ldl, const double* dinv, double* B, int m, long ldb, double* gws, hipStream_t st,
+                 const StrassenWs* sw) {
   if (n <= LEAF_TRSM) {
     const bool ok = gws != nullptr && n % NB == 0 && m >= 4 * NB && (m % 2 == 0) && (ldb % 2 == 0) &&
                     ((reinterpret_cast<uintptr_t>(B) & 15) == 0) && ((long)n * ldb * 8 < 0x7FFFFFFFL);
@@ -508,13 +600,19 @@ int trsm_forward(const double* L, int n, long ldl, const double* dinv, double* B
     return trsm_forward_blocked(L, n, ldl, dinv, B, m, ldb, st);
   }
   const int n1 = split_point(n);
-  int rc = trsm_forward(L, n1, ldl, dinv, B, m, ldb, gws, st);
+  int rc = trsm_forward(L, n1, ldl, dinv, B, m, ldb, gws, st, sw);
   if (rc) return rc;
-  GemmOpts plain;
   // B2 -= L21 * X1
-  rc = launch_gemm(true, false, n - n1, m, n1, -1.0, L + (long)n1 * ldl, ldl, B, ldb, 1.0, B + (long)n1 * ldb, ldb, plain, st);
+  const double* L21 = L + (long)n1 * ldl;
+  if (sw != nullptr && sw->p != nullptr && n1 >= sw->lim.rows && m >= sw->lim.cols && strassen_shape_ok(n - n1, n1, m) &&
+      strassen_operands_ok(L21, ldl, B, ldb) && sw->elems >= strassen_node_elems(n - n1, n1, m)) {
+    rc = strassen_update(L21, ldl, B, ldb, B + (long)n1 * ldb, ldb, n - n1, n1, m, sw->p, st);
+  } else {
+    GemmOpts plain;
+    rc = launch_gemm(true, false, n - n1, m, n1, -1.0, L21, ldl, B, ldb, 1.0, B + (long)n1 * ldb, ldb, plain, st);
+  }
   if (rc) return rc;
-  return trsm_forward(L + (long)n1 * ldl + n1, n - n1, ldl, dinv + (size_t)(n1 / NB) * NB * NB, B + (long)n1 * ldb, m, ldb, gws, st);
+  return trsm_forward(L + (long)n1 * ldl + n1, n - n1, ldl, dinv + (size_t)(n1 / NB) * NB * NB, B + (long)n1 * ldb, m, ldb, gws, st, sw);
 }
 
 int trsm_backward(const double* L, int n, long ldl, const double* dinv, double* B, int m, long ldb, hipStream_t st) {
@@ -707,8 +805,45 @@ extern "C" int gpmp_potrf_lower_async(double* A, int n, long lda, double* dinv, 
   return potrf_lower(A, n, lda, dinv, info_dev, as_stream(stream));
 }
 
+extern "C" size_t gpmp_strassen_ws_elems(int n, int m) {
+  if (n <= 0 || m <= TRSV_FEW_MAX || n > GPMP_MAX_EXTENT || m > GPMP_MAX_EXTENT) return 0;
+  return strassen_solve_elems(n, m, strassen_limits());
+}
+
+extern "C" void gpmp_set_strassen_thresholds(int min_rows, int min_cols) {
+  std::lock_guard<std::mutex> lk(g_strassen_mu);
+  g_strassen_min_rows = min_rows > 0 ? min_rows : STRASSEN_MIN_ROWS;
+  g_strassen_min_cols = min_cols > 0 ? min_cols : STRASSEN_MIN_COLS;
+}
+
+extern "C" size_t gpmp_debug_strassen_ws_elems(int R, int N) {
+  return (R > 0 && N > 0 && R <= GPMP_MAX_EXTENT && N <= GPMP_MAX_EXTENT && strassen_shape_ok(R, R, N)) ? strassen_node_elems(R, R, N) : 0;
+}
+
+// Test hook: B2 (R x N) -= L21 (R x R) X1 (R x N) by the Strassen step, whatever the thresholds say.
+extern "C" int gpmp_debug_strassen_update(const double* L21, long ldl, const double* X1, long ldx, double* B2, long ldb, int R, int N,
+                                          double* scratch, size_t scratch_elems, gpmp_stream_t stream) {
+  GPMP_ARG(L21 != nullptr, 1, "L21 is NULL");
+  GPMP_ARG(X1 != nullptr, 3, "X1 is NULL");
+  GPMP_ARG(B2 != nullptr, 5, "B2 is NULL");
+  GPMP_ARG(R > 0 && R <= GPMP_MAX_EXTENT && R % (2 * NB) == 0, 7, "R outside [256, GPMP_MAX_EXTENT] or not a multiple of 256");
+  GPMP_ARG(N >= 2 * NB && N <= GPMP_MAX_EXTENT && N % 2 == 0, 8, "N outside [256, GPMP_MAX_EXTENT] or odd");
+  GPMP_ARG(ldl >= R && ldl % 2 == 0, 2, "ldl < R or odd");
+  GPMP_ARG(ldx >= N && ldx % 2 == 0, 4, "ldx < N or odd");
+  GPMP_ARG(ldb >= N && ldb % 2 == 0, 6, "ldb < N or odd");
+  GPMP_ARG(scratch != nullptr && scratch_elems >= strassen_node_elems(R, R, N), 9, "scratch is NULL or below gpmp_debug_strassen_ws_elems");
+  GPMP_ARG(((reinterpret_cast<uintptr_t>(L21) | reinterpret_cast<uintptr_t>(X1) | reinterpret_cast<uintptr_t>(B2) |
+             reinterpret_cast<uintptr_t>(scratch)) & 15) == 0, 1, "an operand is not 16-byte aligned");
+  return strassen_update(L21, ldl, X1, ldx, B2, ldb, R, R, N, scratch, as_stream(stream));
+}
+
 extern "C" int gpmp_potrf_trsm_lower_async(double* A, int n, long lda, double* dinv, int* info_dev, double* B, int m, long ldb,
                                            gpmp_stream_t stream) {
+  return potrf_trsm_lower_ws(A, n, lda, dinv, info_dev, B, m, ldb, nullptr, 0, as_stream(stream));
+}
+
+int gpmp::potrf_trsm_lower_ws(double* A, int n, long lda, double* dinv, int* info_dev, double* B, int m, long ldb, double* sws,
+                              size_t sws_elems, hipStream_t st) {
   GPMP_ARG(A != nullptr, 1, "A is NULL");
   GPMP_ARG(n >= 0 && n <= GPMP_MAX_EXTENT, 2, "n outside [0, GPMP_MAX_EXTENT]");
   GPMP_ARG(lda >= n, 3, "lda < n");
@@ -717,7 +852,13 @@ extern "C" int gpmp_potrf_trsm_lower_async(double* A, int n, long lda, double* d
   GPMP_ARG(B != nullptr, 6, "B is NULL");
   GPMP_ARG(m >= 0 && m <= GPMP_MAX_EXTENT && ldb >= m, 8, "m outside [0, GPMP_MAX_EXTENT] or ldb < m");
   if (n == 0) return 0;
-  hipStream_t st = as_stream(stream);
+  // Strassen scratch given and some update of this solve at or above the thresholds: the solve follows the factorisation on the
+  // caller's stream (with the default thresholds that is n >= 16384, above the solve-along sizes anyway)
+  StrassenWs sw;
+  sw.lim = strassen_limits();
+  const size_t sneed = (sws != nullptr && m > TRSV_FEW_MAX) ? strassen_solve_elems(n, m, sw.lim) : 0;
+  GPMP_ARG(sws_elems >= sneed, 10, "Strassen scratch below gpmp_strassen_ws_elems(n, m)");
+  if (sneed > 0) { sw.p = sws; sw.elems = sws_elems; }
   GPMP_HIP_TRY(hipMemsetAsync(info_dev, 0, sizeof(int), st));
   double* gws = (n > 2 * OUTER_BLOCKS * NB) ? dinv + (size_t)((n + NB - 1) / NB) * NB * NB : nullptr;
   // Chain-bound sizes: the factorisation of n <= 8192 leaves most of the machine idle (3.2 ms for 0.33 ms of MFMA work at
@@ -725,7 +866,7 @@ extern "C" int gpmp_potrf_trsm_lower_async(double* A, int n, long lda, double* d
   // Above that the solve follows the factorisation on the caller's stream: overlapping its leading half with the trailing half of
   // the factorisation gained 5-7 ms of a 950 ms call (two GEMM streams lose ~7 % to each other) and was dropped.
   constexpr int along_above = 2 * OUTER_BLOCKS * NB, along_below = 8192;
-  if (m > TRSV_FEW_MAX && n > along_above && n <= along_below) {
+  if (sneed == 0 && m > TRSV_FEW_MAX && n > along_above && n <= along_below) {
     SolveAlong sa;
     sa.B = B; sa.m = m; sa.ldb = ldb; sa.gws = gws;
     return potrf_lookahead(A, n, lda, dinv, info_dev, st, &sa);
@@ -733,7 +874,7 @@ extern "C" int gpmp_potrf_trsm_lower_async(double* A, int n, long lda, double* d
   int rc = (n <= POTRF_ONE_STREAM_MAX) ? potrf_blocked(A, n, lda, dinv, info_dev, 0, st) : potrf_lookahead(A, n, lda, dinv, info_dev, st);
   if (rc || m == 0) return rc;
   if (m <= TRSV_FEW_MAX) return trsv_few(A, n, lda, dinv, B, m, ldb, 0, st);
-  return trsm_forward(A, n, lda, dinv, B, m, ldb, gws, st);
+  return trsm_forward(A, n, lda, dinv, B, m, ldb, gws, st, sneed > 0 ? &sw : nullptr);
 }
 
 extern "C" int gpmp_trtri_diag_blocks(const double* L, int n, long ldl, double* dinv, gpmp_stream_t stream) {

@@ -140,7 +140,46 @@ __global__ void diag_blocks_kernel(double* __restrict__ T, int n, long ldt, cons
   }
 }
 
+// D = X + sign Y on row-major blocks with their own leading dimensions (the operand sums of a Strassen step, linalg.hip): column
+// pairs with 16-byte accesses, grid-stride over pairs (x) and rows (y, four rows in flight per thread), no atomics.
+__global__ void __launch_bounds__(256) block_sum_kernel(const double* __restrict__ X, long ldx, const double* __restrict__ Y, long ldy,
+                                                        double sign, double* __restrict__ D, long ldd, int rows, int pairs) {
+  for (int c = blockIdx.x * 256 + threadIdx.x; c < pairs; c += gridDim.x * 256) {
+    int r = blockIdx.y;
+    for (; r + 3 * (int)gridDim.y < rows; r += 4 * gridDim.y) {
+      d2 x[4], y[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long rr = r + u * (long)gridDim.y;
+        x[u] = *reinterpret_cast<const d2*>(X + rr * ldx + 2 * c);
+        y[u] = *reinterpret_cast<const d2*>(Y + rr * ldy + 2 * c);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) *reinterpret_cast<d2*>(D + (r + u * (long)gridDim.y) * ldd + 2 * c) = x[u] + sign * y[u];
+    }
+    for (; r < rows; r += gridDim.y)
+      *reinterpret_cast<d2*>(D + (long)r * ldd + 2 * c) =
+          *reinterpret_cast<const d2*>(X + (long)r * ldx + 2 * c) + sign * *reinterpret_cast<const d2*>(Y + (long)r * ldy + 2 * c);
+  }
+}
+
 }  // namespace
+
+int launch_block_sum(const double* X, long ldx, const double* Y, long ldy, double sign, double* D, long ldd, int rows, int cols,
+                     hipStream_t st) {
+  if (rows <= 0 || cols <= 0) return 0;
+  const bool ok = (cols % 2 == 0) && (ldx % 2 == 0) && (ldy % 2 == 0) && (ldd % 2 == 0) && ldx >= cols && ldy >= cols && ldd >= cols &&
+                  ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(D)) & 15) == 0;
+  if (!ok) { set_error("block sum: odd column count or leading dimension, or an operand not 16-byte aligned"); return -1; }
+  const int pairs = cols / 2;
+  const int gx = (pairs + 255) / 256 < 64 ? (pairs + 255) / 256 : 64;
+  // about 16 workgroups per compute unit over the whole grid; a thread keeps four rows in flight
+  int gy = (16 * device_cu_count() + gx - 1) / gx;
+  if (gy > (rows + 3) / 4) gy = (rows + 3) / 4;
+  hipLaunchKernelGGL(block_sum_kernel, dim3(gx, gy), dim3(256), 0, st, X, ldx, Y, ldy, sign, D, ldd, rows, pairs);
+  GPMP_HIP_TRY(hipGetLastError());
+  return 0;
+}
 
 int launch_tril(double* A, int n, long lda, hipStream_t st, int nprob, long prob_stride) {
   if (n <= 1) return 0;

@@ -143,6 +143,28 @@ int gpmp_potrf_lower_async(double* A, int n, long lda, double* dinv, int* info_d
 int gpmp_potrf_trsm_lower_async(double* A, int n, long lda, double* dinv, int* info_dev, double* B, int m, long ldb,
                                 gpmp_stream_t stream);
 
+/* One Strassen level in the large updates of the many-right-hand-side forward solve (7 half-size products for 8; the operand
+ * sums need scratch).  An update B2 -= L21 X1 with R = rows of X1 (n / 2 at the top of an n-row solve) and N columns takes it
+ * when R >= min_rows, N >= min_cols, both extents of L21 are multiples of 256 and N is even; it then uses
+ *     pad16((R / 2)^2) + pad16((R / 2) * Nh) doubles,   Nh = 128 * floor(N / 256),   pad16(v) = v rounded up to 16
+ * (L21 square, as for n a power of two; in general rows / 2 * R / 2 for the first term).
+ * gpmp_strassen_ws_elems(n, m): the largest such need over the updates of an n x m solve under the CURRENT thresholds, 0 when
+ * none qualifies (defaults 8192 rows / 16384 columns: 0 below n = 16384; n = 32768, m = 50002: 67,108,864 + 204,472,320 doubles
+ * = 2.17 GB).  The fused prediction drivers (gpmp_predict_*) reserve it at the END of their workspace -- their gpmp_predict*_ws_elems
+ * include it for the solve's m + 1 + q columns rounded up to even -- and hand it to the solve; gpmp_potrf_trsm_lower_async and
+ * gpmp_trsm_lower carry no scratch of that size and run the plain recursion.  Results differ from the plain recursion in rounding
+ * only (normwise; one level multiplies the error constant by a small factor).
+ * gpmp_set_strassen_thresholds: process-wide, thread-safe; a value <= 0 restores that default.  Size the workspace and call the
+ * driver under the same setting: a workspace query and a driver call that disagree end in an argument error, not an overrun.
+ * gpmp_debug_strassen_update (test hook): B2 (R x N) -= L21 (R x R) X1 (R x N) through the step whatever the thresholds are;
+ * R a multiple of 256, N >= 256 even, even leading dimensions, 16-byte aligned operands, scratch of
+ * gpmp_debug_strassen_ws_elems(R, N) doubles (0 for a shape the step does not take).  Enqueue only. */
+size_t gpmp_strassen_ws_elems(int n, int m);
+void gpmp_set_strassen_thresholds(int min_rows, int min_cols);
+size_t gpmp_debug_strassen_ws_elems(int R, int N);
+int gpmp_debug_strassen_update(const double* L21, long ldl, const double* X1, long ldx, double* B2, long ldb, int R, int N,
+                               double* scratch, size_t scratch_elems, gpmp_stream_t stream);
+
 /* B <- op(L)^-1 B for an n x m row-major B; trans = 0: L, 1: L^T.  Replaces
  * scipy.linalg.solve_triangular (numpy_backend.py:467-468, gpmp/core/linalg.py:41).  If
  * dinv == NULL the diagonal-block inverses are recomputed into `scratch` (gpmp_dinv_elems(n)).
