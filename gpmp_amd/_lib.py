@@ -70,6 +70,10 @@ SIGNATURES = {
     "gpmp_predict_grad_ws_elems": (c_size_t, [c_int, c_int, c_int, c_int]),
     "gpmp_predict_grad": (c_int, [_P, _P, _P, c_long, _P, _P, c_long, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P,
                                   _P, _P, _P, _P, _P, _P]),
+    "gpmp_posterior_weights_ws_elems": (c_size_t, [c_int, c_int]),
+    "gpmp_posterior_weights": (c_int, [_P, _P, _P, c_long, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P]),
+    "gpmp_posterior_mean_ws_elems": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "gpmp_posterior_mean": (c_int, [_P, _P, _P, _P, c_long, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P]),
     "gpmp_reml_ws_elems": (c_size_t, [c_int, c_int]),
     "gpmp_reml": (c_int, [_P, _P, _P, c_long, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P]),
     "gpmp_nll_grad_ws_elems": (c_size_t, [c_int, c_int, c_int]),

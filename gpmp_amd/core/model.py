@@ -90,6 +90,18 @@ class Model:
             dzpv = None if dzpv is None else gnp.to_np(dzpv)
         return zpm, zpv, dzpm, dzpv
 
+    def posterior_mean(self, xi, zi, convert_in=True):
+        """The posterior mean given (xi, zi) as a fitted object (``core.posterior_mean.PosteriorMean``): one factorisation here,
+        then ``post(xt)`` and ``post.mean_and_gradient(xt)`` cost one matrix-free pass over the (i, t) pairs each -- for callers
+        that evaluate the mean on the same data many times (plots, multi-start ascent of an acquisition function, a surrogate
+        inside another code).  Matern covariances with a zero, parameterized or linear-predictor mean, as ``predict_gradient``;
+        a failed factorisation raises numpy.linalg.LinAlgError.  The object keeps a snapshot of the parameters: changing
+        ``covparam`` afterwards does not change it."""
+        from .posterior_mean import PosteriorMean
+
+        xi, zi, _ = utils.ensure_shapes_and_type(xi=xi, zi=zi, convert=convert_in)
+        return PosteriorMean(self, xi, zi)
+
     def loo(self, xi, zi, convert_in=True, convert_out=False):
         """Leave-one-out predictions -- gpmp/core/model.py:309-343."""
         xi_, zi_, _ = utils.ensure_shapes_and_type(xi=xi, zi=zi, convert=convert_in)

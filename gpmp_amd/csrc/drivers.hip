@@ -6,7 +6,8 @@
 //   negative_log_likelihood_zero_mean  (gpmp/core/likelihood.py:18-52)
 //   kriging_predictor_with_zero_mean + _compute_posterior_variance (gpmp/core/kriging.py:35-67,170-199)
 // Linear-predictor mean: REML value, ML / REML value + analytic gradient, leave-one-out, universal kriging and its gradient
-// with respect to the prediction points:
+// with respect to the prediction points, and the weights of the fitted posterior mean (gpmp_posterior_weights; its matrix-free
+// evaluation is posterior_mean.hip):
 //   negative_log_restricted_likelihood        gpmp/core/likelihood.py:92-129   (contrasts W = Q[:, q:], G = W^T K W)
 //   its gradient w.r.t. the covariance parameters  (reference: torch autograd, gpmp/num/torch_backend.py:574-604;
 //                                              criterion wrapper gpmp/kernel/parameter_selection.py:35-124)
@@ -17,7 +18,7 @@
 // (DESIGN.md section 2); the q x q algebra (Cholesky of S and P^T P, S^-1, S^-1 b) runs in one small workgroup on the
 // device, so no driver ever waits for the host.  The mean design P = mean(xi) (n x q, row-major) is passed in: mean
 // functions are user callables in the reference (gpmp/core/model.py:30-52).
-// The host side of the seven drivers is built from the shared steps below the kernels: one workspace layout, the covariance
+// The host side of the eight drivers is built from the shared steps below the kernels: one workspace layout, the covariance
 // setup, factor_and_whiten, predict_solve, launch_meanspace, solve_back, launch_reml_finalize.
 #include "matern_device.h"
 
@@ -302,9 +303,19 @@ __global__ void pgrad_finalize_kernel(double* __restrict__ gm, double* __restric
   }
 }
 
+// alpha <- NaN and beta <- NaN when the factorisation failed, else beta = small[SM_C] (gpmp_posterior_weights)
+__global__ void weights_finalize_kernel(double* __restrict__ alpha, int n, double* __restrict__ beta, int q,
+                                        const double* __restrict__ small, const int* info) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool bad = *info != 0;
+  const double nan = __builtin_nan("");
+  if (i < n && bad) alpha[i] = nan;
+  if (i < q) beta[i] = bad ? nan : small[SM_C + i];
+}
+
 // ---- host side: the steps the drivers share --------------------------------------------------------------------------------
 
-// One workspace layout for all seven drivers.  K, dinv and cd are always there; an entry point names the other groups it uses
+// One workspace layout for all eight drivers.  K, dinv and cd are always there; an entry point names the other groups it uses
 // and nothing else is reserved.  The order of the slots is fixed (K at offset 0: it holds L on return).
 enum : unsigned {
   WS_T = 1u << 0,       // T: L^-1 (gradient, LOO)
@@ -370,6 +381,7 @@ constexpr unsigned USE_LOO = USE_REML | WS_T | WS_X | WS_DCOL;
 constexpr unsigned USE_PREDICT = WS_KIT;
 constexpr unsigned USE_PREDICT_MEAN = WS_KIT | WS_MEAN;
 constexpr unsigned USE_PREDICT_GRAD = WS_KIT | WS_MEAN | WS_PGRAD;
+constexpr unsigned USE_WEIGHTS = WS_W | WS_MEAN | WS_SCAL;     // the weights land in the caller's vectors: no X, no y slot
 
 // The covariance as the drivers hand it on.  Built only after the argument checks have passed theta_host.
 struct Cov {
@@ -740,6 +752,46 @@ extern "C" int gpmp_predict_grad(const double* xi, const double* zi, const doubl
   hipLaunchKernelGGL(pgrad_finalize_kernel, dim3((unsigned)((md + 255) / 256)), dim3(256), 0, st, gzpm_dev,
                      with_variance_gradient ? gzpv_dev : nullptr, J, m, d, q, ws + l.small, ws + l.mu, l.ldm, ws + l.vraw,
                      zero_neg_variances, info_dev);
+  GPMP_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" size_t gpmp_posterior_weights_ws_elems(int n, int q) {
+  return (n > 0 && n <= GPMP_MAX_EXTENT && q >= 0 && q <= QMAX) ? driver_layout(n, 0, 1, q, USE_WEIGHTS).total : 0;
+}
+
+extern "C" int gpmp_posterior_weights(const double* xi, const double* zi, const double* Pi, long ldpi, int n, int d, int q, int p,
+                                      const double* theta_host, int noise, double* ws, double* alpha_dev, double* beta_dev,
+                                      int* info_dev, gpmp_stream_t stream) {
+  GPMP_ARG(xi != nullptr, 1, "xi is NULL");
+  GPMP_ARG(zi != nullptr, 2, "zi is NULL");
+  GPMP_ARG(q >= 0 && q <= QMAX, 7, "q outside [0, GPMP_MAX_RANK - 1]");
+  GPMP_ARG(q == 0 || (Pi != nullptr && ldpi >= q), 3, "Pi is NULL or ldpi < q");
+  GPMP_ARG(n > q && n <= GPMP_MAX_EXTENT, 5, "n <= q or above GPMP_MAX_EXTENT");
+  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM_WIDE, 6, "d outside [1, GPMP_MAX_DIM_WIDE]");
+  GPMP_ARG(p >= 0 && p <= GPMP_MAX_P, 8, "p outside [0, GPMP_MAX_P]");
+  GPMP_ARG(theta_host != nullptr, 9, "theta is NULL");
+  GPMP_ARG(ws != nullptr, 11, "ws is NULL");
+  GPMP_ARG(alpha_dev != nullptr, 12, "alpha_dev is NULL");
+  GPMP_ARG(q == 0 || beta_dev != nullptr, 13, "beta_dev is NULL with q > 0");
+  GPMP_ARG(info_dev != nullptr, 14, "info_dev is NULL");
+  hipStream_t st = as_stream(stream);
+  const Cov cov(theta_host, d, p, noise);
+  const DriverLayout l = driver_layout(n, 0, d, q, USE_WEIGHTS);
+  int rc = factor_and_whiten(cov, l, xi, zi, Pi, ldpi, n, q, ws, info_dev, stream);
+  if (rc) return rc;
+  if (q > 0) {
+    rc = launch_meanspace(l, ws + l.W, l.ldq, Pi, ldpi, n, q, ws, info_dev, stream);
+    if (rc) return rc;
+  }
+  // alpha = K^-1 (z - P beta) = L^-T (w - Wp beta), beta = S^-1 Wp^T w
+  hipLaunchKernelGGL(pgrad_gamma_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ws + l.W, l.ldq, n, q, ws + l.small, alpha_dev);
+  GPMP_HIP_TRY(hipGetLastError());
+  rc = gpmp_trsm_lower(ws + l.K, n, l.ldn, ws + l.dinv, alpha_dev, 1, 1, 1, nullptr, stream);
+  if (rc) return rc;
+  const int len = n > q ? n : q;
+  hipLaunchKernelGGL(weights_finalize_kernel, dim3((len + 255) / 256), dim3(256), 0, st, alpha_dev, n, beta_dev, q, ws + l.small,
+                     info_dev);
   GPMP_HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -33,7 +33,7 @@
  *    under the host sanitizers (gpmp_debug_device_table_selftest).  NOT tested: more than one device ordinal driven from
  *    one process -- the GPU pool this was developed on has one-GPU boxes.
  *  - INPUT DIMENSION: every entry point that takes d accepts 1 <= d <= GPMP_MAX_DIM_WIDE (except the batched small-problem
- *    driver, d <= GPMP_MAX_DIM).  d <= GPMP_MAX_DIM runs the register-tier kernels (length scales in the kernel arguments);
+ *    driver and the matrix-free gpmp_posterior_mean, d <= GPMP_MAX_DIM).  d <= GPMP_MAX_DIM runs the register-tier kernels (length scales in the kernel arguments);
  *    larger d runs the wide-dimension kernels, whose length scales are copied to a stream-ordered device allocation per call
  *    (hipMallocAsync / hipFreeAsync on `stream`; for the gradient trace, inside the caller's workspace).
  *  - covparam layout (gpmp/kernel/matern.py:78-79,88-89): theta = [log sigma^2, log(1/rho_1..d)];
@@ -385,6 +385,36 @@ int gpmp_predict_grad(const double* xi, const double* zi, const double* Pi, long
                       long ldpt, const double* J, int n, int m, int d, int q, int p, const double* theta_host, int noise,
                       int zero_neg_variances, int with_variance_gradient, double* ws, double* zpm_dev, double* zpv_dev,
                       double* gzpm_dev, double* gzpv_dev, int* info_dev, gpmp_stream_t stream);
+
+/* ---- fitted posterior mean: weights once, matrix-free evaluation ------------------------------------------------
+ * The dual form of the predictors above.  With beta = S^-1 P^T K^-1 z and alpha = K^-1 (z - P beta) (q = 0: alpha = K^-1 z),
+ *   mean(x) = sum_i alpha_i k(x, x_i) + p(x)^T beta,      d mean / d x_j = D[alpha]_{.,j} + beta^T J_{.,.,j}
+ * so everything that depends on (xi, zi, theta) is two vectors, and one evaluation is ONE pass over the (i, t) pairs: no Gram
+ * matrix, no factorisation, no n x m block.  Both calls are stateless: the caller owns alpha and beta.
+ *
+ * gpmp_posterior_weights: Gram build, Cholesky, W = L^-1 [zi, Pi], the q x q algebra and one back solve, as the drivers above;
+ * alpha_dev (n) and beta_dev (q; may be NULL only when q = 0) are device vectors.  Pi: n x q (ldpi), 0 <= q < GPMP_MAX_RANK,
+ * n > q, 1 <= d <= GPMP_MAX_DIM_WIDE.  *info_dev as gpmp_predict_mean; when it is non-zero alpha and beta are NaN.
+ * ws: gpmp_posterior_weights_ws_elems(n, q) doubles (holds L on return).  Enqueue only. */
+size_t gpmp_posterior_weights_ws_elems(int n, int q);
+int gpmp_posterior_weights(const double* xi, const double* zi, const double* Pi, long ldpi, int n, int d, int q, int p,
+                           const double* theta_host, int noise, double* ws, double* alpha_dev, double* beta_dev,
+                           int* info_dev, gpmp_stream_t stream);
+
+/* gpmp_posterior_mean: zpm_dev[t] = sum_i alpha_i sigma^2 K_p(h_it) + Pt[t] . beta at m points xt (m x d) and, when gzpm_dev !=
+ * NULL, gzpm_dev[t][j] = sigma^2 rho_j^-2 sum_i alpha_i S(h_it) (x_tj - x_ij) + sum_a beta_a J[(t q + a) d + j] (m x d, row-major)
+ * from the same visit of every entry.  Each sigma^2 K_p(h_it) is the entry gpmp_matern_gram(xi, xt) would write; no diagonal
+ * term is ever added (xt are new points, as in gpmp_predict_grad), and the gradient term of a coincident pair is 0 for every p.
+ * Pt: m x q (ldpt), beta: q, J as gpmp_predict_grad; Pt, beta and J may be NULL when q = 0, J also when gzpm_dev is NULL.
+ * 1 <= d <= GPMP_MAX_DIM (no wide-dimension variant: see INPUT DIMENSION above); 0 <= q < GPMP_MAX_RANK; n and m up to
+ * GPMP_MAX_EXTENT.  The sum over i is split into slices that are added in a fixed order (no atomics): two calls on the same
+ * inputs give the same bits.  ws: gpmp_posterior_mean_ws_elems(n, m, d, gzpm_dev != NULL) doubles (the query with the gradient
+ * covers the call without).  Enqueue only. */
+size_t gpmp_posterior_mean_ws_elems(int n, int m, int d, int with_gradient);
+int gpmp_posterior_mean(const double* xi, const double* alpha, const double* xt, const double* Pt, long ldpt,
+                        const double* beta, const double* J, int n, int m, int d, int q, int p,
+                        const double* theta_host, int noise, double* ws, double* zpm_dev, double* gzpm_dev,
+                        gpmp_stream_t stream);
 
 /* ---- many small problems at once (mini-batch criteria, posterior samplers) ------------------------------------- */
 
