@@ -129,5 +129,5 @@ def check(rc, what):
 
 def host_vec(values):
     """Small host parameter vector -> ctypes double array (kept alive by the caller)."""
-    vals = [float(v) for v in values]
+    vals = values.tolist() if hasattr(values, "tolist") else [float(v) for v in values]
     return (c_double * len(vals))(*vals)

@@ -10,6 +10,7 @@ import torch
 
 from .. import _lib
 from .. import num as gnp
+from . import fused
 from .utils import mean_values as _mean_values
 from ..kernel.matern import MaternCovariance
 
@@ -22,10 +23,10 @@ def _derivative_matrices(model, xi, theta, epsilon):
     out = []
     if isinstance(cov, MaternCovariance):
         lib = _lib.load()
-        hv = _lib.host_vec(theta)
+        hv, noise = fused.stage_theta(cov, gnp._host_params(theta), d)
         for j in range(p):
             D = gnp.alloc_matrix(n, n)
-            _lib.check(lib.gpmp_matern_gram_deriv(gnp._ptr(xi), n, d, cov.p, hv, 1 if cov.noise else 0, j, gnp._ptr(D), gnp._ld(D),
+            _lib.check(lib.gpmp_matern_gram_deriv(gnp._ptr(xi), n, d, cov.p, hv, noise, j, gnp._ptr(D), gnp._ld(D),
                                                   gnp._stream()), "gpmp_matern_gram_deriv")
             out.append(D)
         return out

@@ -12,6 +12,7 @@ K^-1 comes from potrf -> trtri -> T^T T on the MFMA GEMM; the trace against dK/d
 pass (gpmp_matern_grad_trace) that recomputes the scaled differences on the fly and subtracts the
 low-rank part  sum_a F[i,a] G[k,a]  in registers -- K and dK are never stored.
 """
+import ctypes
 import math
 import os
 
@@ -20,29 +21,25 @@ import torch
 
 from .. import _lib
 from .. import num as gnp
+from . import fused
 from .utils import mean_values as _mean_values
 from ..kernel.matern import MaternCovariance
 from .linalg import MeanSpace, covariance_factor
 
 
 def _grad_trace(cov: MaternCovariance, Kinv, xi, covparam, F, G):
-    lib = _lib.load()
     xi = gnp._points(xi)
     n, d = xi.shape
     th = gnp._host_params(covparam)
+    hv, noise = fused.stage_theta(cov, th, d)
     r = F.shape[1]
     Fm, Gm = gnp.as_matrix(F), gnp.as_matrix(G)
     if gnp._ld(Fm) != gnp._ld(Gm):
         Gm = gnp.as_matrix(Gm, copy=True)
         Fm = gnp.as_matrix(Fm, copy=True)
     g = torch.zeros(len(th), dtype=torch.float64, device=xi.device)
-    ws = torch.empty(int(lib.gpmp_grad_ws_elems(n, d)), dtype=torch.float64, device=xi.device)
-    hv = _lib.host_vec(th)
-    _lib.check(
-        lib.gpmp_matern_grad_trace(gnp._ptr(Kinv), gnp._ld(Kinv), gnp._ptr(xi), n, d, cov.p, hv, 1 if cov.noise else 0,
-                                   gnp._ptr(Fm), gnp._ptr(Gm), r, gnp._ld(Fm), gnp._ptr(g), gnp._ptr(ws), gnp._stream()),
-        "gpmp_matern_grad_trace",
-    )
+    fused.call_driver("gpmp_matern_grad_trace", _lib.load().gpmp_grad_ws_elems(n, d), Kinv, gnp._ld(Kinv), xi, n, d, cov.p, hv, noise,
+                      Fm, Gm, r, gnp._ld(Fm), g, fused.WS)
     return 0.5 * gnp.to_np(g)
 
 
@@ -100,8 +97,7 @@ class REMLAnalytic:
 
 
 # ---- many small problems in one call ------------------------------------------------------------------
-BATCH_MAX_N = 4096      # GPMP_BATCH_MAX_N (include/gpmp_hip.h)
-BATCH_MAX_Q = 16        # GPMP_BATCH_MAX_Q
+BATCH_MAX_N, BATCH_MAX_Q = fused.limits.BATCH_MAX_N, fused.limits.BATCH_MAX_Q
 
 
 def batch_qualifies(model, use_mean=False):
@@ -153,7 +149,7 @@ def batch_values_and_gradients(model, covparams, batches, want_grad=True, use_me
     d = int(xs[0].shape[1])
     nmax = max(ns)
     # (the batched driver keeps its parameters in fixed-width blocks: d <= 64; wider inputs go one problem at a time)
-    if nmax > BATCH_MAX_N or d > 64 or any(int(x.shape[1]) != d for x in xs):
+    if nmax > BATCH_MAX_N or d > fused.limits.MAX_DIM or any(int(x.shape[1]) != d for x in xs):
         return None
     Ps, q = None, 0
     if use_mean:
@@ -192,16 +188,11 @@ def batch_values_and_gradients(model, covparams, batches, want_grad=True, use_me
         Pm = torch.zeros((B * nmax, q), dtype=torch.float64, device=dev).index_copy_(0, dest, torch.cat(Ps)) if q else None
     sx, sz, sp = (0, 0, 0) if one_data else (nmax * d, nmax, nmax * max(q, 1))
     th = numpy.ascontiguousarray(numpy.asarray(covparams, dtype=numpy.float64))
+    hv, noise = fused.stage_theta(cov, th, d)
     shared = th.ndim == 1
     ntheta = th.shape[-1]
     if not shared and th.shape[0] != B:
         raise ValueError("covparams must be one vector or one row per problem")
-    noise = 1 if cov.noise else 0
-    if ntheta != 1 + noise + d:
-        raise ValueError("covparam length does not match 1 + noise + d")
-    hv = _lib.host_vec(th.reshape(-1))
-    import ctypes
-
     n_host = (ctypes.c_int * B)(*ns)
     ws = torch.empty(int(lib.gpmp_batch_ws_elems(nmax, d, q, B, 1 if want_grad else 0)), dtype=torch.float64, device=dev)
     values = torch.empty(B, dtype=torch.float64, device=dev)

@@ -19,17 +19,11 @@ import numpy
 import torch
 
 from .. import num as gnp
+from . import fused
 from .utils import mean_values as _mean_values
-from ..config import get_config
+from ..kernel.matern import MaternCovariance
 from .linalg import covariance_factor
 from ..num.householder import HouseholderQR as _Reflectors
-
-
-def _chunk_cols(n, m):
-    budget = get_config().predict_chunk_bytes
-    per_col = 8 * max(n, 1)
-    mc = max(256, budget // per_col)
-    return int(min(m, mc)) if m > 0 else 0
 
 
 class _Predictor:
@@ -154,7 +148,7 @@ class _ContrastPredictor:
 
 def _run(model, xi, zi_centered, xt, use_mean, want_lambda, contrast=None):
     n, m = xi.shape[0], xt.shape[0]
-    mc = _chunk_cols(n, m)
+    mc = fused.chunk_cols(n, m)
     if contrast is not None:
         pred = _ContrastPredictor(model, xi, zi_centered, reference_formula=(contrast == "reference"))
     else:
@@ -243,56 +237,39 @@ def fused_prediction(model, xi, zi, xt):
     most of a small prediction (n = 128, m = 500, constant mean: 0.55 ms against 0.3)."""
     import os
 
-    from ..kernel.matern import MaternCovariance
-
     cov = model.covariance
     if os.environ.get("GPMP_PREDICT_FUSED", "1") == "0" or not isinstance(cov, MaternCovariance):
         return None
-    if model.meantype not in ("zero", "parameterized", "linear_predictor") or model.covparam is None:
+    if model.meantype not in fused.MEAN_TYPES or model.covparam is None or cov.p > fused.limits.MAX_P:
+        return None
+    if model.meantype == "parameterized" and model.meanparam is None:
         return None
     if not (isinstance(xi, torch.Tensor) and isinstance(xt, torch.Tensor)) or xt is xi:     # (xt is xi: the reference's identity
         return None                                                                        #  dispatch puts the nugget on K(xi, xt))
     n, m = int(xi.shape[0]), int(xt.shape[0])
-    if n < 1 or m < 1 or xi.dim() != 2 or xt.dim() != 2 or _chunk_cols(n, m) < m:
+    if n < 1 or m < 1 or xi.dim() != 2 or xt.dim() != 2 or fused.chunk_cols(n, m) < m:
         return None
-    d = int(xi.shape[1])
+    try:                        # a wrong parameter count, a mean design whose width changes: the general route states the error
+        st = fused.Staged(model, xi, zi)
+        q = st.q
+        if st.Pi is not None and (q < 1 or q > fused.limits.MAX_RANK - 1 or n <= q):
+            return None
+        Xt = gnp._points(xt)
+        Pt, _, prior_mean, _ = st.at(Xt)
+    except ValueError:
+        return None
     lib = gnp._lib.load()
-    theta = gnp._host_params(model.covparam)
-    if cov.p > 16 or len(theta) != 1 + (1 if cov.noise else 0) + d:
-        return None
-    zt_prior_mean = 0.0
-    zc = gnp.asarray(zi).reshape(-1)
-    Pi = Pt = None
-    if model.meantype == "parameterized":
-        if model.meanparam is None:
-            return None
-        zc = zc - _mean_values(model, xi, model.meanparam).reshape(-1)
-        zt_prior_mean = _mean_values(model, xt, model.meanparam).reshape(-1)
-    elif model.meantype == "linear_predictor":
-        Pi = gnp.as_matrix(_mean_values(model, xi, model.meanparam))
-        Pt = gnp.as_matrix(_mean_values(model, xt, model.meanparam))
-        q = int(Pi.shape[1])
-        if q < 1 or q > 71 or n <= q or int(Pt.shape[1]) != q:
-            return None
-    X, Xt, zc = gnp._points(xi), gnp._points(xt), zc.contiguous()
-    dev = X.device
-    zpm = torch.empty(m, dtype=torch.float64, device=dev)
-    zpv = torch.empty(m, dtype=torch.float64, device=dev)
-    info = torch.zeros(1, dtype=torch.int32, device=dev)
-    hv = gnp._lib.host_vec(theta)
-    noise = 1 if cov.noise else 0
-    if Pi is None:
-        ws = torch.empty(int(lib.gpmp_predict_ws_elems(n, m)), dtype=torch.float64, device=dev)
-        gnp._lib.check(lib.gpmp_predict_zero_mean(gnp._ptr(X), gnp._ptr(zc), gnp._ptr(Xt), n, m, d, cov.p, hv, noise, 0, gnp._ptr(ws),
-                                                  gnp._ptr(zpm), gnp._ptr(zpv), gnp._ptr(info), gnp._stream()), "gpmp_predict_zero_mean")
+    zpm = torch.empty(m, dtype=torch.float64, device=st.X.device)
+    zpv = torch.empty(m, dtype=torch.float64, device=st.X.device)
+    if st.Pi is None:
+        k = fused.call_driver("gpmp_predict_zero_mean", lib.gpmp_predict_ws_elems(n, m), st.X, st.zc, Xt, n, m, st.d, st.p, st.hv,
+                              st.noise, 0, fused.WS, zpm, zpv, fused.INFO)
     else:
-        ws = torch.empty(int(lib.gpmp_predict_mean_ws_elems(n, m, q)), dtype=torch.float64, device=dev)
-        gnp._lib.check(lib.gpmp_predict_mean(gnp._ptr(X), gnp._ptr(zc), gnp._ptr(Pi), gnp._ld(Pi), gnp._ptr(Xt), gnp._ptr(Pt), gnp._ld(Pt),
-                                             n, m, d, q, cov.p, hv, noise, 0, gnp._ptr(ws), gnp._ptr(zpm), gnp._ptr(zpv), gnp._ptr(info),
-                                             gnp._stream()), "gpmp_predict_mean")
-    if int(info.item()) != 0:
+        k = fused.call_driver("gpmp_predict_mean", lib.gpmp_predict_mean_ws_elems(n, m, q), st.X, st.zc, st.Pi, fused.ld(st.Pi), Xt, Pt,
+                              fused.ld(Pt), n, m, st.d, q, st.p, st.hv, st.noise, 0, fused.WS, zpm, zpv, fused.INFO)
+    if k != 0:
         return None
-    return zpm, zpv, zt_prior_mean
+    return zpm, zpv, (0.0 if prior_mean is None else prior_mean)
 
 
 def select_predictor(model, xi, zi, xt, return_lambdas=True):
