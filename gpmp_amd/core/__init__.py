@@ -1,5 +1,5 @@
 """gpmp_amd.core -- GP model facade and its numerical routines (gpmp/core counterpart)."""
 from .model import Model
-from .posterior_mean import PosteriorMean
+from .posterior_mean import PosteriorMean, PosteriorMeans
 
-__all__ = ["Model", "PosteriorMean"]
+__all__ = ["Model", "PosteriorMean", "PosteriorMeans"]

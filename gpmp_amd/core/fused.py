@@ -96,7 +96,8 @@ def _mean_jacobian(model, xt, mean_gradient):
 
 class Staged:
     """What the fused drivers take from a model and its data (xi, zi), prepared once: the points ``X`` (n x d, contiguous), the
-    observations centred by a parameterized mean ``zc``, the mean design ``Pi`` (n x q, or None with q = 0), the covariance
+    observations centred by a parameterized mean ``zc`` (a vector; with ``columns`` the n x s matrix of s observation vectors on the
+    same points, each column centred), the mean design ``Pi`` (n x q, or None with q = 0), the covariance
     parameters (``hv`` for the drivers, ``theta`` the same numbers as a host array, ``p``, ``noise``) and the mean (``mean``,
     ``meantype``, ``meanparam``).
 
@@ -104,7 +105,7 @@ class Staged:
     ``meanparam`` are the attributes the array-level routes (``kriging._Predictor``, the wide Gram route) read from a model, so the
     object is passed to them as it is."""
 
-    def __init__(self, model, xi, zi):
+    def __init__(self, model, xi, zi, columns=False):
         cov = self.covariance = model.covariance
         self.X = gnp._points(xi)
         self.n, self.d = self.X.shape
@@ -113,12 +114,15 @@ class Staged:
         self.mean, self.meantype = model.mean, model.meantype
         mp = model.meanparam
         self.meanparam = mp.detach().clone() if isinstance(mp, torch.Tensor) else (None if mp is None else numpy.array(mp, copy=True))
-        zc = gnp.asarray(zi).reshape(-1)
+        zc = gnp.asarray(zi)
+        if columns and (zc.dim() != 2 or zc.shape[0] != self.n):
+            raise ValueError(f"the observation columns have shape {tuple(zc.shape)}, expected ({self.n}, s)")
+        zc = zc if columns else zc.reshape(-1)
         if zc.dtype != torch.float64:
             zc = zc.to(torch.float64)
         self.Pi, self.q = None, 0
         if self.meantype == "parameterized":
-            zc = zc - _mean_values(self, self.X, self.meanparam).reshape(-1)
+            zc = zc - _mean_values(self, self.X, self.meanparam).reshape((-1, 1) if columns else (-1,))
         elif self.meantype == "linear_predictor":
             self.Pi = gnp.as_matrix(_mean_values(self, self.X, self.meanparam))
             self.q = self.Pi.shape[1]

@@ -102,6 +102,17 @@ class Model:
         xi, zi, _ = utils.ensure_shapes_and_type(xi=xi, zi=zi, convert=convert_in)
         return PosteriorMean(self, xi, zi)
 
+    def posterior_means(self, xi, zi_columns, convert_in=True):
+        """``posterior_mean`` for s observation vectors on the same points: ``zi_columns`` is (n, s) (several responses of one
+        design, or the residuals of conditional sample paths) and ``post(xt)`` is (m, s).  One factorisation for all columns; an
+        evaluation computes every covariance entry once and contracts it against all columns (value only, see
+        ``core.posterior_mean.PosteriorMeans``).  s above GPMP_MAX_COLUMNS raises ValueError, a failed factorisation
+        numpy.linalg.LinAlgError."""
+        from .posterior_mean import PosteriorMeans
+
+        xi, _, _ = utils.ensure_shapes_and_type(xi=xi, convert=convert_in)
+        return PosteriorMeans(self, xi, gnp.asarray(zi_columns) if convert_in else zi_columns)
+
     def loo(self, xi, zi, convert_in=True, convert_out=False):
         """Leave-one-out predictions -- gpmp/core/model.py:309-343."""
         xi_, zi_, _ = utils.ensure_shapes_and_type(xi=xi, zi=zi, convert=convert_in)
@@ -150,6 +161,9 @@ class Model:
 
     def conditional_sample_paths(self, ztsim, xi_ind, zi, xt_ind, lambda_t, convert_out=True):
         return sample_paths.conditional_sample_paths(self, ztsim, xi_ind, zi, xt_ind, lambda_t, convert_out=convert_out)
+
+    def conditional_sample_paths_from_data(self, ztsim, xi, xi_ind, zi, xt, xt_ind, convert_out=True):
+        return sample_paths.conditional_sample_paths_from_data(self, ztsim, xi, xi_ind, zi, xt, xt_ind, convert_out=convert_out)
 
     def conditional_sample_paths_parameterized_mean(self, ztsim, xi, xi_ind, zi, xt, xt_ind, lambda_t, convert_out=True):
         return sample_paths.conditional_sample_paths_parameterized_mean(self, ztsim, xi, xi_ind, zi, xt, xt_ind, lambda_t,

@@ -10,6 +10,10 @@ gpmp_posterior_mean)
 everything that depends on the data is two vectors.  ``PosteriorMean`` owns device copies of xi, alpha and beta and a snapshot of
 the model's parameters; it holds no factor and no library state.  Input dimensions above GPMP_MAX_DIM (64) have no matrix-free
 kernel: the value is then K(xt, xi) alpha by chunks of xt on the wide Gram route, the gradient gpmp_predict_grad_reduce.
+
+``PosteriorMeans`` is the same for s observation vectors on one design (gpmp_posterior_weights_multi / gpmp_posterior_mean_multi):
+one factorisation, the weights A = K^-1 (Z - P B) (n x s) and B (q x s), and per evaluation one pass in which every covariance
+entry is computed once and contracted against all columns by fp64 matrix instructions.  Value only.
 """
 import torch
 
@@ -18,6 +22,7 @@ from . import fused
 from .utils import ensure_shapes_and_type
 
 MAX_DIM = fused.limits.MAX_DIM
+MAX_COLUMNS = 4096          # GPMP_MAX_COLUMNS of include/gpmp_hip.h
 
 
 class PosteriorMean:
@@ -98,3 +103,62 @@ class PosteriorMean:
         if convert_out:
             return gnp.to_np(zpm), gnp.to_np(gm)
         return zpm, gm
+
+
+class PosteriorMeans:
+    """The posterior means of ``model`` given xi and the s columns of ``zi_columns`` (n x s), as a callable: ``post(xt)`` is (m, s),
+    column c the posterior mean for the observations ``zi_columns[:, c]``.  Built by ``Model.posterior_means``; the parameter
+    snapshot is that of ``PosteriorMean``."""
+
+    def __init__(self, model, xi, zi_columns):
+        fused.check_matern_model(model, "posterior_means")
+        xi = gnp._points(xi)
+        if xi.shape[0] < 1:
+            raise ValueError("posterior_means needs at least one observation")
+        st = self._st = fused.Staged(model, xi.clone(), zi_columns, columns=True)
+        n, q, s = st.n, st.q, st.zc.shape[1]
+        if not 1 <= s <= MAX_COLUMNS:
+            raise ValueError(f"posterior_means takes 1 to {MAX_COLUMNS} observation columns, got {s}")
+        self.s = s
+        self.A = torch.empty((n, s), dtype=torch.float64, device=st.X.device)
+        self.B = torch.empty((q, s), dtype=torch.float64, device=st.X.device) if q else None
+        fused.call_driver("gpmp_posterior_weights_multi", gnp._lib.load().gpmp_posterior_weights_multi_ws_elems(n, s, q), st.X, st.zc, s,
+                          st.Pi, fused.ld(st.Pi), n, s, st.d, q, st.p, st.hv, st.noise, fused.WS, self.A, s, self.B, s, fused.INFO, n=n,
+                          who="posterior_means")
+
+    xi = property(lambda self: self._st.X)
+    n = property(lambda self: self._st.n)
+    d = property(lambda self: self._st.d)
+    q = property(lambda self: self._st.q)
+
+    def _kernel(self, xt, Pt):
+        """gpmp_posterior_mean_multi: the matrix-free pass (d <= GPMP_MAX_DIM)."""
+        st, m, s = self._st, xt.shape[0], self.s
+        out = torch.empty((m, s), dtype=torch.float64, device=xt.device)
+        fused.call_driver("gpmp_posterior_mean_multi", gnp._lib.load().gpmp_posterior_mean_multi_ws_elems(st.n, m, s, st.d), st.X, self.A, s,
+                          xt, Pt, fused.ld(Pt), self.B, s, st.n, m, s, st.d, st.q, st.p, st.hv, st.noise, fused.WS, out, s)
+        return out
+
+    def _wide(self, xt, Pt):
+        """d > GPMP_MAX_DIM: K(xt_chunk, xi) A on the wide Gram route."""
+        st, m = self._st, xt.shape[0]
+        mc = fused.chunk_cols(st.n, m, floor=1)
+        parts = []
+        for j0 in range(0, m, mc):
+            Kc = gnp.as_matrix(gnp.asarray(st.covariance(xt[j0 : j0 + mc].contiguous(), st.X, st.covparam)))
+            parts.append(gnp.matmul(Kc, self.A))
+        out = parts[0] if len(parts) == 1 else torch.cat(parts)
+        return out if Pt is None else out + gnp.matmul(Pt, self.B)
+
+    def __call__(self, xt, convert_in=True, convert_out=True):
+        _, _, xt = ensure_shapes_and_type(xi=self.xi, xt=xt, convert=convert_in)
+        xt = gnp._points(xt)
+        m, d = xt.shape
+        if m == 0:
+            out = torch.zeros((0, self.s), dtype=torch.float64, device=self.xi.device)
+        else:
+            Pt, _, prior_mean, _ = self._st.at(xt)
+            out = (self._kernel if d <= MAX_DIM else self._wide)(xt, Pt)
+            if prior_mean is not None:
+                out = out + prior_mean.reshape(-1, 1)
+        return gnp.to_np(out) if convert_out else out

@@ -46,3 +46,21 @@ def conditional_sample_paths_parameterized_mean(model, ztsim, xi, xi_ind, zi, xt
     delta = zi_centered.reshape(-1, 1) - ztsim_[xi_ind, :]
     out = ztsim_[xt_ind, :] + gnp.matmul(gnp.asarray(lambda_t).T.contiguous(), delta) + zt_prior_mean
     return gnp.to_np(out) if convert_out else out
+
+
+def conditional_sample_paths_from_data(model, ztsim, xi, xi_ind, zi, xt, xt_ind, convert_out: bool = True):
+    """The conditioned paths without kriging weights: column c of lambda_t^T (zi - ztsim[xi_ind]) is the kriging mean of the data
+    zi - ztsim[xi_ind, c], so the result is ztsim[xt_ind] + PosteriorMeans(model, xi, zi[:, None] - ztsim[xi_ind])(xt) -- one
+    factorisation and one matrix-free pass for all paths, no n x m matrix.  Zero, parameterized and linear-predictor means alike
+    (a parameterized mean is centred per column and added back, the universal-kriging term is inside the means)."""
+    import torch
+
+    from .posterior_mean import PosteriorMeans
+
+    ztsim_ = gnp.asarray(ztsim)
+    xi_ind = torch.as_tensor(gnp.to_np(xi_ind), device=ztsim_.device).long().reshape(-1)
+    xt_ind = torch.as_tensor(gnp.to_np(xt_ind), device=ztsim_.device).long().reshape(-1)
+    delta = gnp.asarray(zi).reshape(-1, 1) - ztsim_[xi_ind, :]
+    post = PosteriorMeans(model, gnp.asarray(xi), delta)
+    out = ztsim_[xt_ind, :] + post(gnp.asarray(xt), convert_in=False, convert_out=False)
+    return gnp.to_np(out) if convert_out else out

@@ -6,8 +6,9 @@
 //   negative_log_likelihood_zero_mean  (gpmp/core/likelihood.py:18-52)
 //   kriging_predictor_with_zero_mean + _compute_posterior_variance (gpmp/core/kriging.py:35-67,170-199)
 // Linear-predictor mean: REML value, ML / REML value + analytic gradient, leave-one-out, universal kriging and its gradient
-// with respect to the prediction points, and the weights of the fitted posterior mean (gpmp_posterior_weights; its matrix-free
-// evaluation is posterior_mean.hip):
+// with respect to the prediction points, and the weights of the fitted posterior mean (gpmp_posterior_weights, and
+// gpmp_posterior_weights_multi for many observation columns; the matrix-free evaluations are posterior_mean.hip and
+// posterior_mean_multi.hip):
 //   negative_log_restricted_likelihood        gpmp/core/likelihood.py:92-129   (contrasts W = Q[:, q:], G = W^T K W)
 //   its gradient w.r.t. the covariance parameters  (reference: torch autograd, gpmp/num/torch_backend.py:574-604;
 //                                              criterion wrapper gpmp/kernel/parameter_selection.py:35-124)
@@ -18,7 +19,7 @@
 // (DESIGN.md section 2); the q x q algebra (Cholesky of S and P^T P, S^-1, S^-1 b) runs in one small workgroup on the
 // device, so no driver ever waits for the host.  The mean design P = mean(xi) (n x q, row-major) is passed in: mean
 // functions are user callables in the reference (gpmp/core/model.py:30-52).
-// The host side of the eight drivers is built from the shared steps below the kernels: one workspace layout, the covariance
+// The host side of the nine drivers is built from the shared steps below the kernels: one workspace layout, the covariance
 // setup, factor_and_whiten, predict_solve, launch_meanspace, solve_back, launch_reml_finalize.
 #include "matern_device.h"
 
@@ -313,9 +314,57 @@ __global__ void weights_finalize_kernel(double* __restrict__ alpha, int n, doubl
   if (i < q) beta[i] = bad ? nan : small[SM_C + i];
 }
 
+// ---- many observation columns on one design (gpmp_posterior_weights_multi) ---------------------------------------------------
+// Y[i] = [Z_i1 .. Z_is, P_i1 .. P_iq]
+__global__ void pack_cols_kernel(const double* __restrict__ Z, long ldz, const double* __restrict__ P, long ldp, int n, int s, int q,
+                                 double* __restrict__ Y, long ldy) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int w = s + q;
+  if (idx >= (long)n * w) return;
+  const long i = idx / w;
+  const int c = (int)(idx - i * w);
+  Y[i * ldy + c] = c < s ? Z[i * ldz + c] : P[i * ldp + (c - s)];
+}
+
+// B = S^-1 C  (q x s; C = Wp^T Wz, row a at C[a * ldc])
+__global__ void cols_beta_kernel(const double* __restrict__ Sinv, long lds, const double* __restrict__ C, long ldc, int q, int s,
+                                 double* __restrict__ B, long ldb) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= q * s) return;
+  const int a = idx / s, c = idx - a * s;
+  double v = 0.0;
+  for (int b = 0; b < q; ++b) v += Sinv[(long)a * lds + b] * C[(long)b * ldc + c];
+  B[(long)a * ldb + c] = v;
+}
+
+// Wz <- Wz - Wp B in place: W = [Wz | Wp] (n x (s + q), ldw)
+__global__ void cols_residual_kernel(double* __restrict__ W, long ldw, int n, int s, int q, const double* __restrict__ B, long ldb) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)n * s) return;
+  const long i = idx / s;
+  const int c = (int)(idx - i * s);
+  double v = W[i * ldw + c];
+  for (int a = 0; a < q; ++a) v -= W[i * ldw + s + a] * B[(long)a * ldb + c];
+  W[i * ldw + c] = v;
+}
+
+// A <- X (n x s), or NaN when the factorisation failed; then B <- NaN too
+__global__ void cols_finalize_kernel(const double* __restrict__ X, long ldx, int n, int s, int q, double* __restrict__ A, long lda,
+                                     double* __restrict__ B, long ldb, const int* info) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool bad = *info != 0;
+  const double nan = __builtin_nan("");
+  if (idx < (long)n * s) {
+    const long i = idx / s;
+    const int c = (int)(idx - i * s);
+    A[i * lda + c] = bad ? nan : X[i * ldx + c];
+  }
+  if (bad && idx < (long)q * s) B[(idx / s) * ldb + idx % s] = nan;
+}
+
 // ---- host side: the steps the drivers share --------------------------------------------------------------------------------
 
-// One workspace layout for all eight drivers.  K, dinv and cd are always there; an entry point names the other groups it uses
+// One workspace layout for all nine drivers.  K, dinv and cd are always there; an entry point names the other groups it uses
 // and nothing else is reserved.  The order of the slots is fixed (K at offset 0: it holds L on return).
 enum : unsigned {
   WS_T = 1u << 0,       // T: L^-1 (gradient, LOO)
@@ -327,12 +376,13 @@ enum : unsigned {
   WS_SCAL = 1u << 6,    // scal: [0] log-det, [1] quadratic form
   WS_DCOL = 1u << 7,    // dcol: diag(K^-1) (LOO); cd then serves n columns
   WS_PGRAD = 1u << 8,   // y, vraw, mu, red: gradient of the prediction
+  WS_COLS = 1u << 9,    // Wm = L^-1 [Z | P] for m observation COLUMNS (n x ldm) and C = Wp^T Wz ((1 + q) x ldm)
 };
 struct DriverLayout {
   long ldn, ldm, ldq;
-  size_t K, dinv, T, W, X, F, G, Kit, Gm, PtP, Sinv, small, scal, D, dcol, cd, y, vraw, mu, red, gws, sws, sws_elems, total;
+  size_t K, dinv, T, W, X, F, G, Kit, Gm, PtP, Sinv, small, scal, D, dcol, cd, y, vraw, mu, red, gws, Wm, C, sws, sws_elems, total;
 };
-// m = 0 for the drivers without prediction points
+// m = 0 for the drivers without prediction points; the observation columns s of gpmp_posterior_weights_multi
 DriverLayout driver_layout(int n, int m, int d, int q, unsigned use) {
   DriverLayout l = {};
   l.ldn = pad16(n);
@@ -365,6 +415,10 @@ DriverLayout driver_layout(int n, int m, int d, int q, unsigned use) {
     l.red = c.take(gpmp_predict_grad_reduce_ws_elems(n, m, d));
   }
   if (use & WS_FG) l.gws = c.take(gpmp_grad_ws_elems(n, d));
+  if (use & WS_COLS) {
+    l.Wm = c.take((size_t)n * l.ldm);
+    l.C = c.take((size_t)(1 + q) * l.ldm);
+  }
   // last, so that every other slot stays where it was: the Strassen scratch of the prediction solve's large updates (nothing below
   // the thresholds, see gpmp_strassen_ws_elems), sized for the solve's m + 1 + q columns rounded up to even
   if (use & WS_KIT) {
@@ -382,6 +436,7 @@ constexpr unsigned USE_PREDICT = WS_KIT;
 constexpr unsigned USE_PREDICT_MEAN = WS_KIT | WS_MEAN;
 constexpr unsigned USE_PREDICT_GRAD = WS_KIT | WS_MEAN | WS_PGRAD;
 constexpr unsigned USE_WEIGHTS = WS_W | WS_MEAN | WS_SCAL;     // the weights land in the caller's vectors: no X, no y slot
+constexpr unsigned USE_WEIGHTS_MULTI = WS_MEAN | WS_COLS;
 
 // The covariance as the drivers hand it on.  Built only after the argument checks have passed theta_host.
 struct Cov {
@@ -791,6 +846,65 @@ extern "C" int gpmp_posterior_weights(const double* xi, const double* zi, const 
   if (rc) return rc;
   const int len = n > q ? n : q;
   hipLaunchKernelGGL(weights_finalize_kernel, dim3((len + 255) / 256), dim3(256), 0, st, alpha_dev, n, beta_dev, q, ws + l.small,
+                     info_dev);
+  GPMP_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" size_t gpmp_posterior_weights_multi_ws_elems(int n, int s, int q) {
+  if (n < 1 || n > GPMP_MAX_EXTENT || s < 1 || s > GPMP_MAX_COLUMNS || q < 0 || q > QMAX || n <= q) return 0;
+  return driver_layout(n, s, 1, q, USE_WEIGHTS_MULTI).total;
+}
+
+extern "C" int gpmp_posterior_weights_multi(const double* xi, const double* Z, long ldz, const double* Pi, long ldpi, int n, int s,
+                                            int d, int q, int p, const double* theta_host, int noise, double* ws, double* A_dev,
+                                            long lda, double* B_dev, long ldb, int* info_dev, gpmp_stream_t stream) {
+  GPMP_ARG(xi != nullptr, 1, "xi is NULL");
+  GPMP_ARG(Z != nullptr, 2, "Z is NULL");
+  GPMP_ARG(s >= 1 && s <= GPMP_MAX_COLUMNS, 7, "s outside [1, GPMP_MAX_COLUMNS]");
+  GPMP_ARG(ldz >= s, 3, "ldz < s");
+  GPMP_ARG(q >= 0 && q <= QMAX, 9, "q outside [0, GPMP_MAX_RANK - 1]");
+  GPMP_ARG(q == 0 || (Pi != nullptr && ldpi >= q), 4, "Pi is NULL or ldpi < q");
+  GPMP_ARG(n > q && n <= GPMP_MAX_EXTENT, 6, "n <= q or above GPMP_MAX_EXTENT");
+  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM_WIDE, 8, "d outside [1, GPMP_MAX_DIM_WIDE]");
+  GPMP_ARG(p >= 0 && p <= GPMP_MAX_P, 10, "p outside [0, GPMP_MAX_P]");
+  GPMP_ARG(theta_host != nullptr, 11, "theta is NULL");
+  GPMP_ARG(ws != nullptr, 13, "ws is NULL");
+  GPMP_ARG(A_dev != nullptr && lda >= s, 14, "A_dev is NULL or lda < s");
+  GPMP_ARG(q == 0 || (B_dev != nullptr && ldb >= s), 16, "B_dev is NULL or ldb < s with q > 0");
+  GPMP_ARG(info_dev != nullptr, 18, "info_dev is NULL");
+  hipStream_t st = as_stream(stream);
+  const Cov cov(theta_host, d, p, noise);
+  const DriverLayout l = driver_layout(n, s, d, q, USE_WEIGHTS_MULTI);
+  double* K = ws + l.K;
+  double* dinv = ws + l.dinv;
+  double* W = ws + l.Wm;                       // [Wz | Wp], n x (s + q)
+  const long ldw = l.ldm;
+  int rc = gpmp_matern_gram(xi, nullptr, n, n, cov.d, cov.p, cov.theta, cov.noise, cov.diag, 1, K, l.ldn, stream);
+  if (rc) return rc;
+  rc = gpmp_potrf_lower_async(K, n, l.ldn, dinv, info_dev, stream);
+  if (rc) return rc;
+  const long nw = (long)n * (s + q), ns = (long)n * s;
+  hipLaunchKernelGGL(pack_cols_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, Z, ldz, Pi, ldpi, n, s, q, W, ldw);
+  GPMP_HIP_TRY(hipGetLastError());
+  rc = gpmp_trsm_lower(K, n, l.ldn, dinv, W, s + q, ldw, 0, nullptr, stream);
+  if (rc) return rc;
+  if (q > 0) {
+    // S^-1 and the info word from the mean-space step on [last column of Wz | Wp]; then B = S^-1 Wp^T Wz and Wz <- Wz - Wp B
+    rc = launch_meanspace(l, W + (s - 1), ldw, Pi, ldpi, n, q, ws, info_dev, stream);
+    if (rc) return rc;
+    rc = gpmp_coldots(W, n, s, ldw, W + s, q, ldw, ws + l.C, l.ldm, ws + l.cd, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cols_beta_kernel, dim3((q * s + 255) / 256), dim3(256), 0, st, ws + l.Sinv, l.ldq, ws + l.C, l.ldm, q, s, B_dev,
+                       ldb);
+    GPMP_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cols_residual_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, W, ldw, n, s, q, B_dev, ldb);
+    GPMP_HIP_TRY(hipGetLastError());
+  }
+  // A = K^-1 (Z - P B) = L^-T (Wz - Wp B)
+  rc = gpmp_trsm_lower(K, n, l.ldn, dinv, W, s, ldw, 1, nullptr, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(cols_finalize_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, W, ldw, n, s, q, A_dev, lda, B_dev, ldb,
                      info_dev);
   GPMP_HIP_TRY(hipGetLastError());
   return 0;

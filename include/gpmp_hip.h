@@ -33,7 +33,7 @@
  *    under the host sanitizers (gpmp_debug_device_table_selftest).  NOT tested: more than one device ordinal driven from
  *    one process -- the GPU pool this was developed on has one-GPU boxes.
  *  - INPUT DIMENSION: every entry point that takes d accepts 1 <= d <= GPMP_MAX_DIM_WIDE (except the batched small-problem
- *    driver and the matrix-free gpmp_posterior_mean, d <= GPMP_MAX_DIM).  d <= GPMP_MAX_DIM runs the register-tier kernels (length scales in the kernel arguments);
+ *    driver and the matrix-free gpmp_posterior_mean / gpmp_posterior_mean_multi, d <= GPMP_MAX_DIM).  d <= GPMP_MAX_DIM runs the register-tier kernels (length scales in the kernel arguments);
  *    larger d runs the wide-dimension kernels, whose length scales are copied to a stream-ordered device allocation per call
  *    (hipMallocAsync / hipFreeAsync on `stream`; for the gradient trace, inside the caller's workspace).
  *  - covparam layout (gpmp/kernel/matern.py:78-79,88-89): theta = [log sigma^2, log(1/rho_1..d)];
@@ -61,6 +61,7 @@ typedef void* gpmp_stream_t;
                                     (n = 131072 squared is in the tests), extents and launch arithmetic are 32-bit */
 #define GPMP_BATCH_MAX_N 4096 /* largest (padded) problem size of the batched small-problem driver */
 #define GPMP_BATCH_MAX_Q 16   /* largest number of mean-design columns of the batched small-problem driver */
+#define GPMP_MAX_COLUMNS 4096 /* largest number of observation columns s of the many-column posterior mean */
 
 int gpmp_hip_abi_version(void);
 /* Last error text of the calling thread (HIP error string or argument message). */
@@ -415,6 +416,32 @@ int gpmp_posterior_mean(const double* xi, const double* alpha, const double* xt,
                         const double* beta, const double* J, int n, int m, int d, int q, int p,
                         const double* theta_host, int noise, double* ws, double* zpm_dev, double* gzpm_dev,
                         gpmp_stream_t stream);
+
+/* ---- the same for MANY observation columns on one design (conditional sample paths, several responses) ----------
+ * Column c of Z (n x s, row-major, ldz) is one observation vector; the covariance, the points and the mean design are shared,
+ * so K is factored once and the weights are A = K^-1 (Z - Pi B) (n x s, lda) and B = S^-1 Pi^T K^-1 Z (q x s, ldb).
+ *
+ * gpmp_posterior_weights_multi: Gram build, Cholesky, W = L^-1 [Z | Pi] in one solve of s + q columns, the q x q algebra of the
+ * drivers above, B, and one back solve of s columns.  1 <= s <= GPMP_MAX_COLUMNS, 0 <= q < GPMP_MAX_RANK, n > q,
+ * 1 <= d <= GPMP_MAX_DIM_WIDE; ldz, lda >= s; with q > 0 ldpi >= q and ldb >= s (Pi and B_dev may be NULL only when q = 0).
+ * *info_dev as gpmp_posterior_weights; when it is non-zero A and B are NaN.
+ * ws: gpmp_posterior_weights_multi_ws_elems(n, s, q) doubles (holds L on return; 0 for arguments out of range).  Enqueue only. */
+size_t gpmp_posterior_weights_multi_ws_elems(int n, int s, int q);
+int gpmp_posterior_weights_multi(const double* xi, const double* Z, long ldz, const double* Pi, long ldpi,
+                                 int n, int s, int d, int q, int p, const double* theta_host, int noise, double* ws,
+                                 double* A_dev, long lda, double* B_dev, long ldb, int* info_dev, gpmp_stream_t stream);
+
+/* gpmp_posterior_mean_multi: O_dev[t][c] = sum_i sigma^2 K_p(h_it) A[i][c] + sum_a Pt[t][a] B[a][c] at m points xt (m x d) for
+ * the s columns at once (O: m x s, ldo >= s), value only.  Every sigma^2 K_p(h_it) is evaluated once per block of 64 columns --
+ * it is the entry gpmp_matern_gram(xi, xt) would write -- and contracted against the columns by fp64 matrix instructions; no
+ * n x m block is stored and no diagonal term is added.  Nothing beyond column s of a row of A, B or O is read or written.
+ * 1 <= d <= GPMP_MAX_DIM; 1 <= s <= GPMP_MAX_COLUMNS; 0 <= q < GPMP_MAX_RANK (Pt, B may be NULL when q = 0).  The sum over i is
+ * split into slices that are added in a fixed order (no atomics): two calls on the same inputs give the same bits.
+ * ws: gpmp_posterior_mean_multi_ws_elems(n, m, s, d) doubles (0 for arguments out of range).  Enqueue only. */
+size_t gpmp_posterior_mean_multi_ws_elems(int n, int m, int s, int d);
+int gpmp_posterior_mean_multi(const double* xi, const double* A, long lda, const double* xt, const double* Pt, long ldpt,
+                              const double* B, long ldb, int n, int m, int s, int d, int q, int p,
+                              const double* theta_host, int noise, double* ws, double* O_dev, long ldo, gpmp_stream_t stream);
 
 /* ---- many small problems at once (mini-batch criteria, posterior samplers) ------------------------------------- */
 
