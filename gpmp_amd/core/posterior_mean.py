@@ -13,7 +13,9 @@ kernel: the value is then K(xt, xi) alpha by chunks of xt on the wide Gram route
 
 ``PosteriorMeans`` is the same for s observation vectors on one design (gpmp_posterior_weights_multi / gpmp_posterior_mean_multi):
 one factorisation, the weights A = K^-1 (Z - P B) (n x s) and B (q x s), and per evaluation one pass in which every covariance
-entry is computed once and contracted against all columns by fp64 matrix instructions.  Value only.
+entry is computed once and contracted against all columns by fp64 matrix instructions.  ``PosteriorMeans.mean_and_gradient`` adds
+the Jacobian of the s outputs from the same kind of pass (gpmp_posterior_mean_multi_grad): value and gradient are d + 1 components
+per (point, column), all contracted from the same entries.
 """
 import torch
 
@@ -23,6 +25,10 @@ from .utils import ensure_shapes_and_type
 
 MAX_DIM = fused.limits.MAX_DIM
 MAX_COLUMNS = 4096          # GPMP_MAX_COLUMNS of include/gpmp_hip.h
+# PosteriorMeans.mean_and_gradient below this many columns: one gpmp_posterior_mean call per column.  Measured on one MI355X at
+# n = 32768, m = 50000, d = 8, p = 2 (tools/posterior_mean_multi_grad_bench.py): gpmp_posterior_mean with the gradient 5.04 ms per
+# column; gpmp_posterior_mean_multi_grad 18.7 ms at s = 1 and 21.3 ms at s = 16, so three columns are cheaper one by one, four are not.
+GRAD_SINGLE_BELOW = 4
 
 
 class PosteriorMean:
@@ -107,8 +113,9 @@ class PosteriorMean:
 
 class PosteriorMeans:
     """The posterior means of ``model`` given xi and the s columns of ``zi_columns`` (n x s), as a callable: ``post(xt)`` is (m, s),
-    column c the posterior mean for the observations ``zi_columns[:, c]``.  Built by ``Model.posterior_means``; the parameter
-    snapshot is that of ``PosteriorMean``."""
+    column c the posterior mean for the observations ``zi_columns[:, c]``; ``post.mean_and_gradient(xt)`` returns (O, G) with G of
+    shape (m, s, d), the Jacobian of the s outputs at each point.  Built by ``Model.posterior_means``; the parameter snapshot is
+    that of ``PosteriorMean``."""
 
     def __init__(self, model, xi, zi_columns):
         fused.check_matern_model(model, "posterior_means")
@@ -162,3 +169,45 @@ class PosteriorMeans:
             if prior_mean is not None:
                 out = out + prior_mean.reshape(-1, 1)
         return gnp.to_np(out) if convert_out else out
+
+    def _kernel_grad(self, xt, Pt, J):
+        """gpmp_posterior_mean_multi_grad: value and Jacobian from one matrix-free pass (d <= GPMP_MAX_DIM); G is (m, d, s)."""
+        st, m, s = self._st, xt.shape[0], self.s
+        out = torch.empty((m, s), dtype=torch.float64, device=xt.device)
+        G = torch.empty((m, st.d, s), dtype=torch.float64, device=xt.device)
+        if s < GRAD_SINGLE_BELOW:                # the single-column kernel, column by column
+            zpm, gm = torch.empty(m, dtype=torch.float64, device=xt.device), torch.empty((m, st.d), dtype=torch.float64, device=xt.device)
+            for c in range(s):
+                fused.call_driver("gpmp_posterior_mean", gnp._lib.load().gpmp_posterior_mean_ws_elems(st.n, m, st.d, 1), st.X,
+                                  self.A[:, c].contiguous(), xt, Pt, fused.ld(Pt), None if self.B is None else self.B[:, c].contiguous(), J,
+                                  st.n, m, st.d, st.q, st.p, st.hv, st.noise, fused.WS, zpm, gm)
+                out[:, c], G[:, :, c] = zpm, gm
+            return out, G
+        fused.call_driver("gpmp_posterior_mean_multi_grad", gnp._lib.load().gpmp_posterior_mean_multi_grad_ws_elems(st.n, m, s, st.d), st.X,
+                          self.A, s, xt, Pt, fused.ld(Pt), self.B, s, J, st.n, m, s, st.d, st.q, st.p, st.hv, st.noise, fused.WS, out, s, G, s)
+        return out, G
+
+    def _wide_grad(self, xt, Pt, J):
+        """d > GPMP_MAX_DIM: the value as ``_wide``, the gradient column by column through gpmp_predict_grad_reduce."""
+        G = torch.stack([fused.grad_reduce(self._st, xt, self.A[:, c].contiguous(), None)[0] for c in range(self.s)], dim=2)
+        if J is not None:
+            G = G + torch.einsum("ac,tad->tdc", self.B, J)
+        return self._wide(xt, Pt), G.contiguous()
+
+    def mean_and_gradient(self, xt, mean_gradient=None, convert_in=True, convert_out=True):
+        """(O, G) at xt: O (m, s) as ``post(xt)``, G (m, s, d) with G[t, c] the gradient of output c at x_t (with
+        ``convert_out=False`` a permuted view of the (m, d, s) device buffer the kernel writes).  ``mean_gradient(x, meanparam)`` as
+        in ``PosteriorMean.mean_and_gradient``; a parameterized mean adds its prior gradient to every column."""
+        _, _, xt = ensure_shapes_and_type(xi=self.xi, xt=xt, convert=convert_in)
+        xt = gnp._points(xt)
+        m, d = xt.shape
+        if m == 0:
+            out = torch.zeros((0, self.s), dtype=torch.float64, device=self.xi.device)
+            G = torch.zeros((0, d, self.s), dtype=torch.float64, device=self.xi.device)
+        else:
+            Pt, J, prior_mean, prior_grad = self._st.at(xt, True, mean_gradient)
+            out, G = (self._kernel_grad if d <= MAX_DIM else self._wide_grad)(xt, Pt, J)
+            if prior_mean is not None:
+                out, G = out + prior_mean.reshape(-1, 1), G + prior_grad.reshape(m, d, 1)
+        G = G.permute(0, 2, 1)
+        return (gnp.to_np(out), gnp.to_np(G)) if convert_out else (out, G)

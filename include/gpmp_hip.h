@@ -33,7 +33,7 @@
  *    under the host sanitizers (gpmp_debug_device_table_selftest).  NOT tested: more than one device ordinal driven from
  *    one process -- the GPU pool this was developed on has one-GPU boxes.
  *  - INPUT DIMENSION: every entry point that takes d accepts 1 <= d <= GPMP_MAX_DIM_WIDE (except the batched small-problem
- *    driver and the matrix-free gpmp_posterior_mean / gpmp_posterior_mean_multi, d <= GPMP_MAX_DIM).  d <= GPMP_MAX_DIM runs the register-tier kernels (length scales in the kernel arguments);
+ *    driver and the matrix-free gpmp_posterior_mean / gpmp_posterior_mean_multi / gpmp_posterior_mean_multi_grad, d <= GPMP_MAX_DIM).  d <= GPMP_MAX_DIM runs the register-tier kernels (length scales in the kernel arguments);
  *    larger d runs the wide-dimension kernels, whose length scales are copied to a stream-ordered device allocation per call
  *    (hipMallocAsync / hipFreeAsync on `stream`; for the gradient trace, inside the caller's workspace).
  *  - covparam layout (gpmp/kernel/matern.py:78-79,88-89): theta = [log sigma^2, log(1/rho_1..d)];
@@ -432,7 +432,7 @@ int gpmp_posterior_weights_multi(const double* xi, const double* Z, long ldz, co
                                  double* A_dev, long lda, double* B_dev, long ldb, int* info_dev, gpmp_stream_t stream);
 
 /* gpmp_posterior_mean_multi: O_dev[t][c] = sum_i sigma^2 K_p(h_it) A[i][c] + sum_a Pt[t][a] B[a][c] at m points xt (m x d) for
- * the s columns at once (O: m x s, ldo >= s), value only.  Every sigma^2 K_p(h_it) is evaluated once per block of 64 columns --
+ * the s columns at once (O: m x s, ldo >= s), value only (with the Jacobian: gpmp_posterior_mean_multi_grad).  Every sigma^2 K_p(h_it) is evaluated once per block of 64 columns --
  * it is the entry gpmp_matern_gram(xi, xt) would write -- and contracted against the columns by fp64 matrix instructions; no
  * n x m block is stored and no diagonal term is added.  Nothing beyond column s of a row of A, B or O is read or written.
  * 1 <= d <= GPMP_MAX_DIM; 1 <= s <= GPMP_MAX_COLUMNS; 0 <= q < GPMP_MAX_RANK (Pt, B may be NULL when q = 0).  The sum over i is
@@ -442,6 +442,24 @@ size_t gpmp_posterior_mean_multi_ws_elems(int n, int m, int s, int d);
 int gpmp_posterior_mean_multi(const double* xi, const double* A, long lda, const double* xt, const double* Pt, long ldpt,
                               const double* B, long ldb, int n, int m, int s, int d, int q, int p,
                               const double* theta_host, int noise, double* ws, double* O_dev, long ldo, gpmp_stream_t stream);
+
+/* gpmp_posterior_mean_multi_grad: O_dev as gpmp_posterior_mean_multi and, from the same pass, the Jacobian of the s outputs,
+ * G_dev[(t d + j) ldg + c] = sigma^2 rho_j^-2 sum_i S(h_it) (x_tj - x_ij) A[i][c] + sum_a B[a][c] J[(t q + a) d + j]
+ * (m x d x s, columns fastest, ldg >= s; S, the coincident-pair rule -- the term is 0 for every p -- and the layout of J are those
+ * of gpmp_posterior_mean / gpmp_predict_grad).  Value and gradient are d + 1 components per (point, column); each is a
+ * contraction of the same columns of A by fp64 matrix instructions, and every entry's distance, square root, exponential and
+ * both polynomials are evaluated once per block of components and columns.  The value's entries are those gpmp_matern_gram(xi, xt)
+ * would write; the gradient accumulates the differences of the SCALED points (one more rounding per point than gpmp_posterior_mean,
+ * relative 2^-53 (|x_tj| + |x_ij|) / |x_tj - x_ij| per term).  Nothing beyond column s of a row of A, B, O or G is read or written.
+ * 1 <= d <= GPMP_MAX_DIM; 1 <= s <= GPMP_MAX_COLUMNS; 0 <= q < GPMP_MAX_RANK; lda, ldo, ldg >= s; with q > 0 ldpt >= q, ldb >= s and
+ * Pt, B, J are required (all three may be NULL when q = 0).  The sum over i is split into slices that are added in a fixed order
+ * (no atomics): two calls on the same inputs give the same bits.
+ * ws: gpmp_posterior_mean_multi_grad_ws_elems(n, m, s, d) doubles (0 for arguments out of range).  Enqueue only. */
+size_t gpmp_posterior_mean_multi_grad_ws_elems(int n, int m, int s, int d);
+int gpmp_posterior_mean_multi_grad(const double* xi, const double* A, long lda, const double* xt, const double* Pt, long ldpt,
+                                   const double* B, long ldb, const double* J, int n, int m, int s, int d, int q, int p,
+                                   const double* theta_host, int noise, double* ws, double* O_dev, long ldo, double* G_dev,
+                                   long ldg, gpmp_stream_t stream);
 
 /* ---- many small problems at once (mini-batch criteria, posterior samplers) ------------------------------------- */
 
