@@ -31,6 +31,16 @@ MAX_COLUMNS = 4096          # GPMP_MAX_COLUMNS of include/gpmp_hip.h
 GRAD_SINGLE_BELOW = 4
 
 
+def _wide_product(st, xt, W):
+    """d > GPMP_MAX_DIM: K(xt_chunk, xi) @ W by chunks of xt on the wide Gram route; W a vector (n) or a matrix (n x s)."""
+    mc = fused.chunk_cols(st.n, xt.shape[0], floor=1)
+    parts = []
+    for j0 in range(0, xt.shape[0], mc):
+        Kc = gnp.as_matrix(gnp.asarray(st.covariance(xt[j0 : j0 + mc].contiguous(), st.X, st.covparam)))
+        parts.append(gnp.matmul(Kc, W))
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
 class PosteriorMean:
     """The posterior mean of ``model`` given (xi, zi), as a callable.
 
@@ -68,13 +78,8 @@ class PosteriorMean:
 
     def _wide(self, xt, Pt, J, gradient):
         """d > GPMP_MAX_DIM: K(xt_chunk, xi) alpha on the wide Gram route, the gradient through gpmp_predict_grad_reduce."""
-        st, m = self._st, xt.shape[0]
-        mc = fused.chunk_cols(st.n, m, floor=1)
-        parts = []
-        for j0 in range(0, m, mc):
-            Kc = gnp.as_matrix(gnp.asarray(st.covariance(xt[j0 : j0 + mc].contiguous(), st.X, st.covparam)))
-            parts.append(gnp.matmul(Kc, self.alpha).reshape(-1))
-        zpm = parts[0] if len(parts) == 1 else torch.cat(parts)
+        st = self._st
+        zpm = _wide_product(st, xt, self.alpha).reshape(-1)
         if Pt is not None:
             zpm = zpm + gnp.matmul(Pt, self.beta).reshape(-1)
         gm = None
@@ -148,27 +153,8 @@ class PosteriorMeans:
 
     def _wide(self, xt, Pt):
         """d > GPMP_MAX_DIM: K(xt_chunk, xi) A on the wide Gram route."""
-        st, m = self._st, xt.shape[0]
-        mc = fused.chunk_cols(st.n, m, floor=1)
-        parts = []
-        for j0 in range(0, m, mc):
-            Kc = gnp.as_matrix(gnp.asarray(st.covariance(xt[j0 : j0 + mc].contiguous(), st.X, st.covparam)))
-            parts.append(gnp.matmul(Kc, self.A))
-        out = parts[0] if len(parts) == 1 else torch.cat(parts)
+        out = _wide_product(self._st, xt, self.A)
         return out if Pt is None else out + gnp.matmul(Pt, self.B)
-
-    def __call__(self, xt, convert_in=True, convert_out=True):
-        _, _, xt = ensure_shapes_and_type(xi=self.xi, xt=xt, convert=convert_in)
-        xt = gnp._points(xt)
-        m, d = xt.shape
-        if m == 0:
-            out = torch.zeros((0, self.s), dtype=torch.float64, device=self.xi.device)
-        else:
-            Pt, _, prior_mean, _ = self._st.at(xt)
-            out = (self._kernel if d <= MAX_DIM else self._wide)(xt, Pt)
-            if prior_mean is not None:
-                out = out + prior_mean.reshape(-1, 1)
-        return gnp.to_np(out) if convert_out else out
 
     def _kernel_grad(self, xt, Pt, J):
         """gpmp_posterior_mean_multi_grad: value and Jacobian from one matrix-free pass (d <= GPMP_MAX_DIM); G is (m, d, s)."""
@@ -194,20 +180,34 @@ class PosteriorMeans:
             G = G + torch.einsum("ac,tad->tdc", self.B, J)
         return self._wide(xt, Pt), G.contiguous()
 
-    def mean_and_gradient(self, xt, mean_gradient=None, convert_in=True, convert_out=True):
-        """(O, G) at xt: O (m, s) as ``post(xt)``, G (m, s, d) with G[t, c] the gradient of output c at x_t (with
-        ``convert_out=False`` a permuted view of the (m, d, s) device buffer the kernel writes).  ``mean_gradient(x, meanparam)`` as
-        in ``PosteriorMean.mean_and_gradient``; a parameterized mean adds its prior gradient to every column."""
+    def _evaluate(self, xt, mean_gradient, gradient, convert_in):
+        """(O, G) as device tensors, G in the kernel's layout (m, d, s), or None without ``gradient``."""
         _, _, xt = ensure_shapes_and_type(xi=self.xi, xt=xt, convert=convert_in)
         xt = gnp._points(xt)
         m, d = xt.shape
         if m == 0:
-            out = torch.zeros((0, self.s), dtype=torch.float64, device=self.xi.device)
-            G = torch.zeros((0, d, self.s), dtype=torch.float64, device=self.xi.device)
-        else:
-            Pt, J, prior_mean, prior_grad = self._st.at(xt, True, mean_gradient)
+            dev = self.xi.device
+            return (torch.zeros((0, self.s), dtype=torch.float64, device=dev),
+                    torch.zeros((0, d, self.s), dtype=torch.float64, device=dev) if gradient else None)
+        Pt, J, prior_mean, prior_grad = self._st.at(xt, gradient, mean_gradient)
+        if gradient:
             out, G = (self._kernel_grad if d <= MAX_DIM else self._wide_grad)(xt, Pt, J)
-            if prior_mean is not None:
-                out, G = out + prior_mean.reshape(-1, 1), G + prior_grad.reshape(m, d, 1)
+        else:
+            out, G = (self._kernel if d <= MAX_DIM else self._wide)(xt, Pt), None
+        if prior_mean is not None:
+            out = out + prior_mean.reshape(-1, 1)
+            if gradient:
+                G = G + prior_grad.reshape(m, d, 1)
+        return out, G
+
+    def __call__(self, xt, convert_in=True, convert_out=True):
+        out, _ = self._evaluate(xt, None, False, convert_in)
+        return gnp.to_np(out) if convert_out else out
+
+    def mean_and_gradient(self, xt, mean_gradient=None, convert_in=True, convert_out=True):
+        """(O, G) at xt: O (m, s) as ``post(xt)``, G (m, s, d) with G[t, c] the gradient of output c at x_t (with
+        ``convert_out=False`` a permuted view of the (m, d, s) device buffer the kernel writes).  ``mean_gradient(x, meanparam)`` as
+        in ``PosteriorMean.mean_and_gradient``; a parameterized mean adds its prior gradient to every column."""
+        out, G = self._evaluate(xt, mean_gradient, True, convert_in)
         G = G.permute(0, 2, 1)
         return (gnp.to_np(out), gnp.to_np(G)) if convert_out else (out, G)

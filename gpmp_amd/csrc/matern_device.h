@@ -1,5 +1,7 @@
-// Device helpers shared by the Gram / gradient kernels of gram.hip and the prediction-gradient kernels of predict_grad.hip: the
-// Matern polynomial, the fp64 sqrt / exp used on the hot path, and the host-side coefficient tables and parameter setup.
+// Device helpers shared by the Gram / gradient kernels of gram.hip, the prediction-gradient kernels of predict_grad.hip and the
+// posterior-mean kernels of posterior_mean.hip and posterior_mean_multi.hip: the Matern polynomial, the fp64 sqrt / exp used on the
+// hot path, the lock-step chain and the scale pre-pass of the posterior-mean kernels, and the host-side coefficient tables and
+// parameter setup.
 // Everything is internal to the translation unit that includes it.
 #pragma once
 #include "common.h"
@@ -83,6 +85,58 @@ __device__ __forceinline__ double fast_exp_neg_half(const FastExp& fe, double t)
   for (int j = 11; j >= 0; --j) e = fma(e, r, fe.c[j]);
   const int k = (int)nk;
   return ldexp(e, k < -1100 ? -1100 : k);
+}
+
+// The lock-step chain of the posterior-mean kernels over IB entries, from t^2 = |scaled difference|^2: tt = t, e = exp(-t/2) and
+// kv = sigma^2 K_p = e sum_k qs[k] t^k.  Every step runs across the whole batch before the next one starts: the interleaving keeps
+// the fp64 pipe fed across the dependent sqrt / exp / Horner chain.
+template <int IB>
+__device__ __forceinline__ void matern_lockstep(const FastExp& fe, const double* qs, int pdeg, const double (&t2)[IB], double (&tt)[IB],
+                                                double (&e)[IB], double (&kv)[IB]) {
+#pragma unroll
+  for (int b = 0; b < IB; ++b) tt[b] = fast_sqrt_pos(t2[b], fe.tiny);
+#pragma unroll
+  for (int b = 0; b < IB; ++b) e[b] = fast_exp_neg_half(fe, tt[b]);
+  const double qtop = qs[pdeg];
+#pragma unroll
+  for (int b = 0; b < IB; ++b) kv[b] = qtop;
+  for (int k = pdeg - 1; k >= 0; --k) {
+    const double qk = qs[k];
+#pragma unroll
+    for (int b = 0; b < IB; ++b) kv[b] = fma(kv[b], tt[b], qk);
+  }
+#pragma unroll
+  for (int b = 0; b < IB; ++b) kv[b] = e[b] * kv[b];
+}
+// ... and the gradient weight w = sigma^2 S(h) / (2 c)^2 = e sum_{k>=1} ss[k] t^(k-1) of the same entries; p = 0 has S = -K / (2 t)
+// in these units and the subgradient convention 0 at a coincident pair.
+template <int IB>
+__device__ __forceinline__ void matern_lockstep_w(const double* ss, int pdeg, const double (&tt)[IB], const double (&e)[IB],
+                                                  const double (&kv)[IB], double (&w)[IB]) {
+  if (pdeg == 0) {
+#pragma unroll
+    for (int b = 0; b < IB; ++b) w[b] = tt[b] > 0.0 ? -0.5 * kv[b] / tt[b] : 0.0;
+  } else {
+    const double stop = ss[pdeg];
+#pragma unroll
+    for (int b = 0; b < IB; ++b) w[b] = stop;
+    for (int k = pdeg - 1; k >= 1; --k) {
+      const double sk = ss[k];
+#pragma unroll
+      for (int b = 0; b < IB; ++b) w[b] = fma(w[b], tt[b], sk);
+    }
+#pragma unroll
+    for (int b = 0; b < IB; ++b) w[b] *= e[b];
+  }
+}
+
+// The pre-pass of the posterior-mean kernels: sxi = scale_j xi, a plain product with one rounding, as the Gram kernel stages its
+// points.  P has xi, sxi, scale, n and d.
+template <class P>
+__global__ void scale_points_kernel(P p) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)p.n * p.d) return;
+  p.sxi[idx] = p.scale[idx % p.d] * p.xi[idx];
 }
 
 __device__ __forceinline__ double matern_dk_over_h(const MaternSpec& ms, double h, double& kval) {

@@ -49,12 +49,6 @@ struct PmParams {
   FastExp fe;
 };
 
-__global__ void pm_scale_points_kernel(PmParams p) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)p.n * p.d) return;
-  p.sxi[idx] = p.scale[idx % p.d] * p.xi[idx];
-}
-
 template <int DT, bool G>
 __global__ void __launch_bounds__(64) posterior_mean_kernel(PmParams p) {
   constexpr int GD = G ? DT : 1;
@@ -108,42 +102,13 @@ __global__ void __launch_bounds__(64) posterior_mean_kernel(PmParams p) {
         }
       }
     }
-    double tt[PM_IB], e[PM_IB], poly[PM_IB];
+    double tt[PM_IB], e[PM_IB], kv[PM_IB];
+    matern_lockstep(p.fe, p.qs, pdeg, t2, tt, e, kv);
 #pragma unroll
-    for (int b = 0; b < PM_IB; ++b) tt[b] = fast_sqrt_pos(t2[b], p.fe.tiny);
-#pragma unroll
-    for (int b = 0; b < PM_IB; ++b) e[b] = fast_exp_neg_half(p.fe, tt[b]);
-    const double qtop = p.qs[pdeg];
-#pragma unroll
-    for (int b = 0; b < PM_IB; ++b) poly[b] = qtop;
-    for (int k = pdeg - 1; k >= 0; --k) {
-      const double qk = p.qs[k];
-#pragma unroll
-      for (int b = 0; b < PM_IB; ++b) poly[b] = fma(poly[b], tt[b], qk);
-    }
-    double kv[PM_IB];
-#pragma unroll
-    for (int b = 0; b < PM_IB; ++b) {
-      kv[b] = e[b] * poly[b];
-      av = fma(a[b], kv[b], av);
-    }
+    for (int b = 0; b < PM_IB; ++b) av = fma(a[b], kv[b], av);
     if constexpr (G) {
       double w[PM_IB];
-      if (pdeg == 0) {
-#pragma unroll
-        for (int b = 0; b < PM_IB; ++b) w[b] = tt[b] > 0.0 ? -0.5 * kv[b] / tt[b] : 0.0;
-      } else {
-        const double stop = p.ss[pdeg];
-#pragma unroll
-        for (int b = 0; b < PM_IB; ++b) w[b] = stop;
-        for (int k = pdeg - 1; k >= 1; --k) {
-          const double sk = p.ss[k];
-#pragma unroll
-          for (int b = 0; b < PM_IB; ++b) w[b] = fma(w[b], tt[b], sk);
-        }
-#pragma unroll
-        for (int b = 0; b < PM_IB; ++b) w[b] *= e[b];
-      }
+      matern_lockstep_w(p.ss, pdeg, tt, e, kv, w);
 #pragma unroll
       for (int b = 0; b < PM_IB; ++b) w[b] *= a[b];
 #pragma unroll
@@ -298,7 +263,7 @@ extern "C" int gpmp_posterior_mean(const double* xi, const double* alpha, const 
   gp.p = p;
   fill_fast_exp(gp.fe);
   const long nd = (long)n * d;
-  hipLaunchKernelGGL(pm_scale_points_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, gp);
+  hipLaunchKernelGGL(scale_points_kernel<PmParams>, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, gp);
   GPMP_HIP_TRY(hipGetLastError());
   const dim3 grid((m + PM_TM - 1) / PM_TM, gp.nslices);
   if (d <= 4) launch_tier<4>(gp, grid, st);

@@ -38,6 +38,16 @@ def _resources(src):
     return res
 
 
+def resources_by_makefile(obj):
+    """The resource remarks of one object of csrc/Makefile, compiled by the Makefile's own command (make -n), so that per-file flags
+    are those of the library that is loaded: {kernel: {remark: value}}."""
+    cmd = subprocess.run(["make", "-s", "-n", "-B", obj], cwd=CSRC, capture_output=True, text=True).stdout.split()
+    out = subprocess.run(cmd[:-1] + [os.devnull, "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, capture_output=True, text=True, timeout=900)
+    assert cmd and out.returncode == 0, out.stderr[-2000:]
+    return {b.split()[0]: {k.strip(): int(v) for k, v in re.findall(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", b)}
+            for b in out.stderr.split("Function Name: ")[1:]}
+
+
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 @pytest.mark.parametrize("src, must_match", [
     ("gram.hip", ("gram_kernel_v3", "grad_trace_kernel", "pairwise_kernel", "gram_deriv_kernel")),

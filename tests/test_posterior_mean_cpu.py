@@ -159,7 +159,7 @@ def test_new_kernels_use_no_scratch_and_spill_no_vector_registers():
             res[name][m.group(1).strip()] = int(m.group(2))
     main = [k for k in res if "posterior_mean_kernel" in k]
     assert len(main) == 10, sorted(res)                    # five dimension tiers, with and without the gradient
-    for frag in ("posterior_mean_kernel", "posterior_mean_finalize_kernel", "pm_scale_points_kernel"):
+    for frag in ("posterior_mean_kernel", "posterior_mean_finalize_kernel", "scale_points_kernel"):
         hit = {k: v for k, v in res.items() if frag in k}
         assert hit, (frag, sorted(res))
         for k, v in hit.items():

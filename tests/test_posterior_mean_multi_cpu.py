@@ -1,13 +1,13 @@
 """The many-column posterior mean without a GPU: the four symbols, their workspace queries and argument checks (host code, no
-device), and the compile-time resources of the kernels of csrc/posterior_mean_multi.hip, compiled by the Makefile's own command."""
+device), and the compile-time resources of the kernels of csrc/posterior_mean_multi.hip (value and gradient instances), compiled
+by the Makefile's own command."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
-from .test_kernel_resources_cpu import CSRC, HIPCC
+from .test_kernel_resources_cpu import HIPCC, resources_by_makefile
 from .test_posterior_mean_cpu import lib  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,15 +58,15 @@ def test_argument_checks(lib, fn, order, kw, arg):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_kernels_use_no_scratch_and_spill_no_vector_registers():
-    cmd = subprocess.run(["make", "-s", "-n", "-B", "posterior_mean_multi.o"], cwd=CSRC, capture_output=True, text=True).stdout.split()
-    out = subprocess.run(cmd[:-1] + [os.devnull, "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert cmd and out.returncode == 0, out.stderr[-2000:]
-    res = {b.split()[0]: {k.strip(): int(v) for k, v in re.findall(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", b)}
-           for b in out.stderr.split("Function Name: ")[1:]}
-    main = [k for k in res if "pmm_contract_kernel" in k]
-    assert len(main) == 20, sorted(res)                      # five dimension tiers x 1 .. 4 column tiles
-    assert any("pmm_finalize_kernel" in k for k in res) and any("pmm_scale_points_kernel" in k for k in res)
+def test_value_and_gradient_kernels_use_no_scratch_and_spill_no_vector_registers():
+    """One template serves both entries: its value instances have one component slot (the last template argument)."""
+    res = resources_by_makefile("posterior_mean_multi.o")
+    main = {k: tuple(map(int, re.search(r"pmm_contract_kernelILi(\d+)ELi(\d+)ELi(\d+)EE", k).groups())) for k in res if "pmm_contract_kernel" in k}
+    assert len(main) == 32, sorted(res)
+    value, grad = ({(dt, ct) for dt, ct, nc in main.values() if (nc == 1) == one} for one in (True, False))
+    assert len(value) == 20, sorted(value)                   # five dimension tiers x 1 .. 4 column tiles
+    assert len(grad) == 12, sorted(grad)                     # x_t in registers (d <= 8, d <= 16) or in LDS x 1 .. 4 column tiles
+    assert any("pmm_finalize_kernel" in k for k in res) and any("scale_points_kernel" in k for k in res)
     for k, v in res.items():
         assert v["ScratchSize"] == 0 and v["VGPRs Spill"] == 0, (k, v)
     assert all(res[k]["VGPRs"] <= 256 for k in main)

@@ -1,14 +1,11 @@
 """The many-column posterior mean with its Jacobian without a GPU: the two symbols, the workspace query and the argument checks (host
-code, no device), and the compile-time resources of the kernels of csrc/posterior_mean_multi_grad.hip, compiled by the Makefile's
-own command."""
+code, no device).  The compile-time resources of its kernels: test_posterior_mean_multi_cpu.py."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
-from .test_kernel_resources_cpu import CSRC, HIPCC
 from .test_posterior_mean_cpu import lib  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,18 +42,3 @@ def test_argument_checks(lib, kw, arg):
     a.update(kw)
     rc = lib.gpmp_posterior_mean_multi_grad(*[a[k] for k in ORDER], None)
     assert rc == -arg and b"argument" in lib.gpmp_last_error(), (rc, lib.gpmp_last_error())
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_kernels_use_no_scratch_and_spill_no_vector_registers():
-    cmd = subprocess.run(["make", "-s", "-n", "-B", "posterior_mean_multi_grad.o"], cwd=CSRC, capture_output=True, text=True).stdout.split()
-    out = subprocess.run(cmd[:-1] + [os.devnull, "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert cmd and out.returncode == 0, out.stderr[-2000:]
-    res = {b.split()[0]: {k.strip(): int(v) for k, v in re.findall(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", b)}
-           for b in out.stderr.split("Function Name: ")[1:]}
-    main = [k for k in res if "pmg_contract_kernel" in k]
-    assert len(main) == 12, sorted(res)                      # x_t in registers (d <= 8, d <= 16) or in LDS x 1 .. 4 column tiles
-    assert any("pmg_finalize_kernel" in k for k in res) and any("pmg_scale_points_kernel" in k for k in res)
-    for k, v in res.items():
-        assert v["ScratchSize"] == 0 and v["VGPRs Spill"] == 0, (k, v)
-    assert all(res[k]["VGPRs"] <= 256 for k in main)

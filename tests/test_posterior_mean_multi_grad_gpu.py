@@ -1,7 +1,7 @@
 """PosteriorMeans.mean_and_gradient and the C entry gpmp_posterior_mean_multi_grad on the GPU, against the library's own Gram matrix
 (value), the NumPy restatement (posterior_mean_numpy.py, Jacobian) and the single-column kernel gpmp_posterior_mean.
 
-Tile extents of csrc/posterior_mean_multi_grad.hip this file relies on: a matrix instruction takes 4 observation points, 16 run in
+Tile extents of csrc/posterior_mean_multi.hip (its gradient instances) this file relies on: a matrix instruction takes 4 observation points, 16 run in
 lock step, 32 make an LDS chunk, a slice has at least 128 (n = 1000 at m <= 64: 8 slices of 128 rows, the last of 104 = three
 chunks and a short one; n = 300: 3 slices, the last of 44); a wave owns 16 prediction points, a workgroup 64; a column tile is 16
 wide and a workgroup has 1 to 4 of them (s <= 16, <= 32, <= 48, more), with at most 12 / 8 / 5 / 4 of the d + 1 components per
@@ -13,6 +13,7 @@ import pytest
 from . import posterior_mean_numpy as pmn
 from . import predict_grad_numpy as pgn
 from .test_posterior_mean_gpu import _c_mean, _dev, _model, _problem, env  # noqa: F401
+from .test_posterior_mean_multi_gpu import _c_mean_multi
 
 pytestmark = pytest.mark.gpu
 NS = (1, 3, 4, 5, 15, 16, 17, 31, 32, 33, 127, 128, 129, 1000)
@@ -119,6 +120,23 @@ def test_against_the_single_column_kernel(env, s):
         v, g = _c_mean(env, X, A[:, c].contiguous(), XT, 2, th, 0, Pt, q, B[:, c].contiguous(), J)
         pmn.close(O[:, c].cpu().numpy(), v.cpu().numpy(), 1e-9, ("value", c))
         pmn.close(G[:, :, c].cpu().numpy(), g.cpu().numpy(), 1e-9, ("gradient", c))
+
+
+def test_value_bits_are_those_of_the_value_entry(env):
+    """n <= 128 is one slice in both entries whatever m and s, and component 0 of the gradient pass runs the value entry's code
+    (one kernel template, one finalize kernel): the two O are the same bits, with and without the mean part."""
+    torch, rng = env[3], np.random.default_rng(7)
+    for d in (3, 17):
+        th = _problem(1, 1, d, 0)[3]
+        X, XT, AL = _dev(env, rng.random((128, d))), _dev(env, rng.random((65, d))), _dev(env, rng.standard_normal((128, 65)))
+        Pt, BL, J = _dev(env, rng.standard_normal((65, 2))), _dev(env, rng.standard_normal((2, 65))), _dev(env, rng.standard_normal((65, 2, d)))
+        for n in (5, 128):
+            for s in (17, 65):
+                A, B = AL[:n, :s].contiguous(), BL[:, :s].contiguous()
+                for mean in ((), (Pt, B)):
+                    O = _c_mean_multi(env, X[:n], A, XT, s, 2, th, 0, *mean)
+                    Og, _ = _c_multi_grad(env, X[:n], A, XT, s, 2, th, 0, *mean, *((J,) if mean else ()))
+                    assert torch.equal(O, Og), (d, n, s, len(mean))
 
 
 @pytest.mark.parametrize("kind, d, s", [("zero", 4, 17), ("lin", 4, 17), ("param", 4, 17), ("lin", 70, 17), ("lin", 4, 3)])
