@@ -8,8 +8,11 @@ gpmp_posterior_mean)
     mean(x) = sum_i alpha_i k(x, x_i) + p(x)^T beta,      d mean / d x_j = D[alpha]_{.,j} + beta^T J_{.,.,j}
 
 everything that depends on the data is two vectors.  ``PosteriorMean`` owns device copies of xi, alpha and beta and a snapshot of
-the model's parameters; it holds no factor and no library state.  Input dimensions above GPMP_MAX_DIM (64) have no matrix-free
-kernel: the value is then K(xt, xi) alpha by chunks of xt on the wide Gram route, the gradient gpmp_predict_grad_reduce.
+the model's parameters; it holds no factor and no library state.  Input dimensions above GPMP_MAX_DIM (64) take the value from
+gpmp_posterior_mean_wide, the matrix-free kernel that streams d (s = 1 for ``PosteriorMean``), wherever it was measured to be no
+slower than K(xt, xi) W by chunks of xt on the wide Gram route (``wide_kernel_serves``), and from that route elsewhere.  The
+gradient at d > 64 stays gpmp_predict_grad_reduce: a matrix-free Jacobian at wide d would repeat an entry's 2 d distance
+instructions once per block of components, a cost that grows as d^2 per entry, so it is not built.
 
 ``PosteriorMeans`` is the same for s observation vectors on one design (gpmp_posterior_weights_multi / gpmp_posterior_mean_multi):
 one factorisation, the weights A = K^-1 (Z - P B) (n x s) and B (q x s), and per evaluation one pass in which every covariance
@@ -31,14 +34,38 @@ MAX_COLUMNS = 4096          # GPMP_MAX_COLUMNS of include/gpmp_hip.h
 GRAD_SINGLE_BELOW = 4
 
 
-def _wide_product(st, xt, W):
-    """d > GPMP_MAX_DIM: K(xt_chunk, xi) @ W by chunks of xt on the wide Gram route; W a vector (n) or a matrix (n x s)."""
-    mc = fused.chunk_cols(st.n, xt.shape[0], floor=1)
-    parts = []
-    for j0 in range(0, xt.shape[0], mc):
-        Kc = gnp.as_matrix(gnp.asarray(st.covariance(xt[j0 : j0 + mc].contiguous(), st.X, st.covparam)))
-        parts.append(gnp.matmul(Kc, W))
-    return parts[0] if len(parts) == 1 else torch.cat(parts)
+# gpmp_posterior_mean_wide against the chunked Gram route at d > GPMP_MAX_DIM.  Measured on one MI355X at n = 32768, m = 50000, p = 2
+# (tools/posterior_mean_wide_bench.py, HIP events, ms, kernel / chunked route):
+#   s = 1:   d = 65  16.4 / 23.1    96  22.7 / 28.0    128  29.2 / 32.7    160  36.2 / 37.8    192  43.1 / 42.4    256  57.1 / 52.1
+#            1024  225 / 173
+#   s = 4:   d = 65  16.5 / 20.8    128  29.4 / 29.9          s = 16:  d = 65  16.8 / 20.9    128  29.4 / 29.7
+#   s = 64:  d = 65  24.7 / 20.7    128  39.5 / 29.6    1024  270 / 170
+# so the kernel serves one column up to d = 160 and 2 to 16 columns up to d = 128 (17 to 63 columns were not measured); everything
+# else keeps the chunked route.  The kernel's peak memory is the scaled points (n d doubles, 50 to 340 MB here) against the
+# 12.5 GB Gram block of the chunked route.
+WIDE_KERNEL_MAX_DIM_SINGLE = 160
+WIDE_KERNEL_MAX_DIM = 128
+WIDE_KERNEL_MAX_COLUMNS = 16
+
+
+def wide_kernel_serves(d, s):
+    """Whether gpmp_posterior_mean_wide (not the chunked Gram route) evaluates s columns at input dimension d > GPMP_MAX_DIM."""
+    return d <= WIDE_KERNEL_MAX_DIM_SINGLE if s == 1 else (s <= WIDE_KERNEL_MAX_COLUMNS and d <= WIDE_KERNEL_MAX_DIM)
+
+
+def _wide_value(st, xt, W, s, Pt, B):
+    """The value at d > GPMP_MAX_DIM, (m, s): W the weights (n x s, or a vector with s = 1), B (q x s, or a vector) or None.
+    gpmp_posterior_mean_wide, the matrix-free pass, or K(xt_chunk, xi) @ W by chunks of xt on the wide Gram route plus Pt B."""
+    m = xt.shape[0]
+    if wide_kernel_serves(st.d, s):
+        out = torch.empty((m, s), dtype=torch.float64, device=xt.device)
+        fused.call_driver("gpmp_posterior_mean_wide", gnp._lib.load().gpmp_posterior_mean_wide_ws_elems(st.n, m, s, st.d), st.X, W, s, xt,
+                          Pt, fused.ld(Pt), B, s, st.n, m, s, st.d, st.q, st.p, st.hv, st.noise, fused.WS, out, s)
+        return out
+    mc = fused.chunk_cols(st.n, m, floor=1)
+    out = torch.cat([gnp.matmul(gnp.as_matrix(gnp.asarray(st.covariance(xt[j0 : j0 + mc].contiguous(), st.X, st.covparam))), W.reshape(-1, s))
+                     for j0 in range(0, m, mc)])
+    return out if Pt is None else out + gnp.matmul(Pt, B.reshape(-1, s))
 
 
 class PosteriorMean:
@@ -77,11 +104,9 @@ class PosteriorMean:
         return zpm, gm
 
     def _wide(self, xt, Pt, J, gradient):
-        """d > GPMP_MAX_DIM: K(xt_chunk, xi) alpha on the wide Gram route, the gradient through gpmp_predict_grad_reduce."""
+        """d > GPMP_MAX_DIM: the value from ``_wide_value`` (s = 1), the gradient through gpmp_predict_grad_reduce."""
         st = self._st
-        zpm = _wide_product(st, xt, self.alpha).reshape(-1)
-        if Pt is not None:
-            zpm = zpm + gnp.matmul(Pt, self.beta).reshape(-1)
+        zpm = _wide_value(st, xt, self.alpha, 1, Pt, self.beta).reshape(-1)
         gm = None
         if gradient:
             gm, _ = fused.grad_reduce(st, xt, self.alpha, None)
@@ -152,9 +177,8 @@ class PosteriorMeans:
         return out
 
     def _wide(self, xt, Pt):
-        """d > GPMP_MAX_DIM: K(xt_chunk, xi) A on the wide Gram route."""
-        out = _wide_product(self._st, xt, self.A)
-        return out if Pt is None else out + gnp.matmul(Pt, self.B)
+        """d > GPMP_MAX_DIM: ``_wide_value``."""
+        return _wide_value(self._st, xt, self.A, self.s, Pt, self.B)
 
     def _kernel_grad(self, xt, Pt, J):
         """gpmp_posterior_mean_multi_grad: value and Jacobian from one matrix-free pass (d <= GPMP_MAX_DIM); G is (m, d, s)."""

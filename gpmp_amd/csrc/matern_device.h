@@ -1,5 +1,5 @@
 // Device helpers shared by the Gram / gradient kernels of gram.hip, the prediction-gradient kernels of predict_grad.hip and the
-// posterior-mean kernels of posterior_mean.hip and posterior_mean_multi.hip: the Matern polynomial, the fp64 sqrt / exp used on the
+// posterior-mean kernels of posterior_mean.hip, posterior_mean_multi.hip and posterior_mean_wide.hip: the Matern polynomial, the fp64 sqrt / exp used on the
 // hot path, the lock-step chain and the scale pre-pass of the posterior-mean kernels, and the host-side coefficient tables and
 // parameter setup.
 // Everything is internal to the translation unit that includes it.

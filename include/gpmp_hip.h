@@ -33,9 +33,11 @@
  *    under the host sanitizers (gpmp_debug_device_table_selftest).  NOT tested: more than one device ordinal driven from
  *    one process -- the GPU pool this was developed on has one-GPU boxes.
  *  - INPUT DIMENSION: every entry point that takes d accepts 1 <= d <= GPMP_MAX_DIM_WIDE (except the batched small-problem
- *    driver and the matrix-free gpmp_posterior_mean / gpmp_posterior_mean_multi / gpmp_posterior_mean_multi_grad, d <= GPMP_MAX_DIM).  d <= GPMP_MAX_DIM runs the register-tier kernels (length scales in the kernel arguments);
+ *    driver and the register-tier matrix-free gpmp_posterior_mean / gpmp_posterior_mean_multi / gpmp_posterior_mean_multi_grad,
+ *    d <= GPMP_MAX_DIM; the matrix-free VALUE at any d is gpmp_posterior_mean_wide).  d <= GPMP_MAX_DIM runs the register-tier
+ *    kernels (length scales in the kernel arguments);
  *    larger d runs the wide-dimension kernels, whose length scales are copied to a stream-ordered device allocation per call
- *    (hipMallocAsync / hipFreeAsync on `stream`; for the gradient trace, inside the caller's workspace).
+ *    (hipMallocAsync / hipFreeAsync on `stream`; for the gradient trace and gpmp_posterior_mean_wide, inside the caller's workspace).
  *  - covparam layout (gpmp/kernel/matern.py:78-79,88-89): theta = [log sigma^2, log(1/rho_1..d)];
  *    with `noise` != 0 the layout is [log sigma^2, log sigma_noise^2, log(1/rho_1..d)]
  *    (examples/gpmp_example07_nd_regression.py:95-131).
@@ -407,7 +409,7 @@ int gpmp_posterior_weights(const double* xi, const double* zi, const double* Pi,
  * from the same visit of every entry.  Each sigma^2 K_p(h_it) is the entry gpmp_matern_gram(xi, xt) would write; no diagonal
  * term is ever added (xt are new points, as in gpmp_predict_grad), and the gradient term of a coincident pair is 0 for every p.
  * Pt: m x q (ldpt), beta: q, J as gpmp_predict_grad; Pt, beta and J may be NULL when q = 0, J also when gzpm_dev is NULL.
- * 1 <= d <= GPMP_MAX_DIM (no wide-dimension variant: see INPUT DIMENSION above); 0 <= q < GPMP_MAX_RANK; n and m up to
+ * 1 <= d <= GPMP_MAX_DIM (above: gpmp_posterior_mean_wide with s = 1, value only); 0 <= q < GPMP_MAX_RANK; n and m up to
  * GPMP_MAX_EXTENT.  The sum over i is split into slices that are added in a fixed order (no atomics): two calls on the same
  * inputs give the same bits.  ws: gpmp_posterior_mean_ws_elems(n, m, d, gzpm_dev != NULL) doubles (the query with the gradient
  * covers the call without).  Enqueue only. */
@@ -460,6 +462,23 @@ int gpmp_posterior_mean_multi_grad(const double* xi, const double* A, long lda, 
                                    const double* B, long ldb, const double* J, int n, int m, int s, int d, int q, int p,
                                    const double* theta_host, int noise, double* ws, double* O_dev, long ldo, double* G_dev,
                                    long ldg, gpmp_stream_t stream);
+
+/* gpmp_posterior_mean_wide: the value pass of gpmp_posterior_mean_multi for ANY input dimension 1 <= d <= GPMP_MAX_DIM_WIDE, same
+ * arguments in the same order: O_dev[t][c] = sum_i sigma^2 K_p(h_it) A[i][c] + sum_a Pt[t][a] B[a][c] (O: m x s, ldo >= s).  The
+ * kernel streams d (observation points through LDS, x_t through registers, the length scales staged into ws per call), so it is
+ * the matrix-free route for d > GPMP_MAX_DIM; at d <= GPMP_MAX_DIM it computes what gpmp_posterior_mean_multi computes, more slowly.
+ * The single-column case is s = 1 with lda = ldo = 1 (ldb = 1): alpha as A, beta as B.  Every sigma^2 K_p(h_it) is the entry
+ * gpmp_matern_gram(xi, xt) writes on its wide route -- the dimensions summed in ascending order, no norm expansion -- so points
+ * padded with zero coordinates give the same result; no n x m block is stored and no diagonal term is added.  Nothing beyond
+ * column s of a row of A, B or O is read or written.  1 <= s <= GPMP_MAX_COLUMNS; 0 <= p <= GPMP_MAX_P; 0 <= q < GPMP_MAX_RANK;
+ * lda, ldo >= s; with q > 0 ldpt >= q, ldb >= s and Pt, B are required (both may be NULL when q = 0).  The sum over i is split
+ * into slices that are added in a fixed order (no atomics): two calls on the same inputs give the same bits.  No gradient: at
+ * d > GPMP_MAX_DIM that stays gpmp_predict_grad_reduce.
+ * ws: gpmp_posterior_mean_wide_ws_elems(n, m, s, d) doubles (0 for arguments out of range).  Enqueue only. */
+size_t gpmp_posterior_mean_wide_ws_elems(int n, int m, int s, int d);
+int gpmp_posterior_mean_wide(const double* xi, const double* A, long lda, const double* xt, const double* Pt, long ldpt,
+                             const double* B, long ldb, int n, int m, int s, int d, int q, int p,
+                             const double* theta_host, int noise, double* ws, double* O_dev, long ldo, gpmp_stream_t stream);
 
 /* ---- many small problems at once (mini-batch criteria, posterior samplers) ------------------------------------- */
 
