@@ -5,6 +5,8 @@
 #include <cstdio>
 #include <cstring>
 #include <atomic>
+#include <memory>
+#include <mutex>
 #include <vector>
 #include "../../include/gpmp_hip.h"
 
@@ -145,11 +147,45 @@ int launch_diag_blocks(double* T, int n, long ldt, const double* dinv, hipStream
 int launch_block_sum(const double* X, long ldx, const double* Y, long ldy, double sign, double* D, long ldd, int rows, int cols,
                      hipStream_t st);
 
+// *flag = 1 unless a and b (elems doubles each) agree as 64-bit patterns and *info == 0, else 0: the factor store's key check
+int launch_bits_differ(const double* a, const double* b, size_t elems, const int* info, int* flag, hipStream_t st);
+
 // ---- factorisation + forward solve with the Strassen scratch of the solve's large updates (linalg.hip) -----------------------
 // gpmp_potrf_trsm_lower_async with `sws` (gpmp_strassen_ws_elems(n, m) doubles, or NULL: plain recursion): the fused drivers carve
 // it from their workspace.  sws_elems is what the caller reserved; less than the solve needs is an argument error.
 int potrf_trsm_lower_ws(double* A, int n, long lda, double* dinv, int* info_dev, double* B, int m, long ldb, double* sws,
                         size_t sws_elems, hipStream_t st);
+
+// The solve of potrf_trsm_lower_ws alone, on a factor that exists already (a hit of the factor store): the same kernels on the same
+// operands in the same order as the solve that follows or accompanies the factorisation there, so B comes out bit for bit the same.
+// gws: the caller's own leaf scratch (what lies behind the block inverses of a gpmp_dinv_elems(n) buffer), or NULL for n <= 1024.
+int trsm_lower_as_fused(const double* L, int n, long ldl, const double* dinv, double* gws, double* B, int m, long ldb, double* sws,
+                        size_t sws_elems, hipStream_t st);
+
+// ---- the factor store (linalg.hip; factor_store.h): one factor of K(xi, xi; theta) per device, kept across driver calls -----------
+// A lease is taken before the Gram build and dropped when the driver returns; it holds the device's mutex in between.
+//   mode 0: no store for this call (disabled, too large, stream under capture): factor in the caller's workspace, as without a store
+//   mode 1: hit -- L and dinv hold the factor, the stream is ordered behind its factorisation; skip the Gram build and the potrf
+//   mode 2: miss -- build and factor into L / dinv, then factor_store_publish
+struct FactorLease {
+  int mode = 0;
+  double* L = nullptr;
+  double* dinv = nullptr;
+  hipStream_t st = nullptr;
+  std::shared_ptr<void> owner;
+  std::unique_lock<std::recursive_mutex> lock;
+  FactorLease() = default;
+  FactorLease(const FactorLease&) = delete;
+  FactorLease& operator=(const FactorLease&) = delete;
+  ~FactorLease();                    // records the lease's reads behind everything enqueued on st
+};
+// route: factor_route of the factorisation the caller would run -- part of the key
+int factor_store_acquire(const double* x, int n, int d, int p, int noise, const double* theta_host, double diag, long ldn, int route,
+                         hipStream_t st, FactorLease* lease);
+// Which schedule factors n x n: 0 the one-stream blocked one, 1 the look-ahead.  m > 0: as part of potrf_trsm_lower_ws with m
+// right-hand sides (have_sws: with Strassen scratch), whose solve along takes the look-ahead from 1025 rows on; m = 0: the plain potrf.
+int factor_route(int n, int m, bool have_sws);
+int factor_store_publish(FactorLease* lease, const int* info_dev);
 
 // ---- batched small problems (linalg.hip): `nprob` independent n x n matrices (n <= GPMP_BATCH_MAX_N), a fixed number of
 // elements apart; every step is ONE launch over all problems (blockIdx.y / .z = problem)

@@ -471,21 +471,48 @@ int stage_zp(const double* z, const double* P, long ldp, int n, int q, double* Y
   return 0;
 }
 
-// Gram (lower) -> Cholesky -> W = L^-1 [z, P] -> ln|K|.  Leaves L in ws + l.K, W in ws + l.W, ln|K| in ws + l.scal.
+// Where the factor of a call lives: the K and dinv slots of the caller's workspace, or -- for the drivers that only read L once it
+// exists -- the factor store (common.h), which keeps it for the next call on the same points and parameters.  The drivers that turn
+// L into something else in place (gpmp_nll_grad) or were not asked to (gpmp_loo, the many-column weights) stay in the workspace.
+struct Factor {
+  FactorLease lease;
+  double* K = nullptr;
+  double* dinv = nullptr;
+  bool hit() const { return lease.mode == 1; }
+};
+int locate_factor(const Cov& cov, const DriverLayout& l, const double* x, int n, int route, double* ws, bool store, hipStream_t st,
+                  Factor* f) {
+  f->K = ws + l.K;
+  f->dinv = ws + l.dinv;
+  if (!store) return 0;
+  const int rc = factor_store_acquire(x, n, cov.d, cov.p, cov.noise, cov.theta, cov.diag, l.ldn, route, st, &f->lease);
+  if (rc) return rc;
+  if (f->lease.mode != 0) { f->K = f->lease.L; f->dinv = f->lease.dinv; }
+  return 0;
+}
+
+// Gram (lower) -> Cholesky -> W = L^-1 [z, P] -> ln|K|.  Leaves L in f->K, W in ws + l.W, ln|K| in ws + l.scal.  On a hit of the
+// factor store the first two steps are skipped; the info word is cleared as the factorisation would have.
 int factor_and_whiten(const Cov& cov, const DriverLayout& l, const double* x, const double* z, const double* P, long ldp, int n,
-                      int q, double* ws, int* info_dev, gpmp_stream_t stream) {
-  double* K = ws + l.K;
-  double* dinv = ws + l.dinv;
+                      int q, double* ws, int* info_dev, gpmp_stream_t stream, bool store, Factor* f) {
+  int rc = locate_factor(cov, l, x, n, factor_route(n, 0, false), ws, store, as_stream(stream), f);
+  if (rc) return rc;
   double* W = ws + l.W;
-  int rc = gpmp_matern_gram(x, nullptr, n, n, cov.d, cov.p, cov.theta, cov.noise, cov.diag, 1, K, l.ldn, stream);
-  if (rc) return rc;
-  rc = gpmp_potrf_lower_async(K, n, l.ldn, dinv, info_dev, stream);
-  if (rc) return rc;
+  if (f->hit()) {
+    GPMP_HIP_TRY(hipMemsetAsync(info_dev, 0, sizeof(int), as_stream(stream)));
+  } else {
+    rc = gpmp_matern_gram(x, nullptr, n, n, cov.d, cov.p, cov.theta, cov.noise, cov.diag, 1, f->K, l.ldn, stream);
+    if (rc) return rc;
+    rc = gpmp_potrf_lower_async(f->K, n, l.ldn, f->dinv, info_dev, stream);
+    if (rc) return rc;
+    rc = factor_store_publish(&f->lease, info_dev);
+    if (rc) return rc;
+  }
   rc = stage_zp(z, P, ldp, n, q, W, l.ldq, as_stream(stream));
   if (rc) return rc;
-  rc = gpmp_trsm_lower(K, n, l.ldn, dinv, W, 1 + q, l.ldq, 0, nullptr, stream);
+  rc = gpmp_trsm_lower(f->K, n, l.ldn, f->dinv, W, 1 + q, l.ldq, 0, nullptr, stream);
   if (rc) return rc;
-  return gpmp_logdet_chol(K, n, l.ldn, ws + l.scal, stream);
+  return gpmp_logdet_chol(f->K, n, l.ldn, ws + l.scal, stream);
 }
 
 // Gram of W = L^-1 [z, P] (n x (1 + q), leading dimension ldw) and, with a mean design, P^T P and the q x q algebra.
@@ -512,7 +539,8 @@ int launch_meanspace(const DriverLayout& l, const double* W, long ldw, const dou
 // The common start of gpmp_reml, gpmp_nll_grad and gpmp_loo
 int factor_and_meanspace(const Cov& cov, const DriverLayout& l, const double* x, const double* z, const double* P, long ldp, int n,
                          int q, double* ws, int* info_dev, gpmp_stream_t stream) {
-  const int rc = factor_and_whiten(cov, l, x, z, P, ldp, n, q, ws, info_dev, stream);
+  Factor f;
+  const int rc = factor_and_whiten(cov, l, x, z, P, ldp, n, q, ws, info_dev, stream, false, &f);
   return rc ? rc : launch_meanspace(l, ws + l.W, l.ldq, P, ldp, n, q, ws, info_dev, stream);
 }
 
@@ -534,21 +562,29 @@ int solve_back(const DriverLayout& l, int n, int q, double* ws, gpmp_stream_t st
 // L^-1 [K(xi, xt) | z | P] in ONE solve, in place and panel by panel behind the factorisation at chain-bound sizes (the separate
 // few-column sweep for W was 0.17 ms of a 5.3 ms prediction at n = 4096 and waited for the end of the factorisation; as columns
 // of the solve it is hidden like the rest).  An even column count keeps the LDS-direct GEMM's fast path.
-// Leaves L in ws + l.K, V in ws + l.Kit and W behind it, at ws + l.Kit + m (leading dimension ldm for both).
+// Leaves L in f->K, V in ws + l.Kit and W behind it, at ws + l.Kit + m (leading dimension ldm for both).  On a hit of the factor
+// store the Gram of K and the factorisation are skipped and the solve alone runs, piece for piece as it does beside the factorisation.
 int predict_solve(const Cov& cov, const DriverLayout& l, const double* xi, const double* zi, const double* Pi, long ldpi,
-                  const double* xt, int n, int m, int q, double* ws, int* info_dev, gpmp_stream_t stream) {
+                  const double* xt, int n, int m, int q, double* ws, int* info_dev, gpmp_stream_t stream, Factor* f) {
   hipStream_t st = as_stream(stream);
-  double* K = ws + l.K;
   double* Kit = ws + l.Kit;
-  int rc = gpmp_matern_gram(xi, nullptr, n, n, cov.d, cov.p, cov.theta, cov.noise, cov.diag, 1, K, l.ldn, stream);
+  const int mb = (m + 1 + q) + ((m + 1 + q) & 1);
+  int rc = locate_factor(cov, l, xi, n, factor_route(n, mb, l.sws_elems != 0), ws, true, st, f);
+  if (rc) return rc;
+  if (f->hit()) GPMP_HIP_TRY(hipMemsetAsync(info_dev, 0, sizeof(int), st));
+  else rc = gpmp_matern_gram(xi, nullptr, n, n, cov.d, cov.p, cov.theta, cov.noise, cov.diag, 1, f->K, l.ldn, stream);
   if (rc) return rc;
   rc = gpmp_matern_gram(xi, xt, n, m, cov.d, cov.p, cov.theta, cov.noise, 0.0, 0, Kit, l.ldm, stream);
   if (rc) return rc;
   rc = stage_zp(zi, Pi, ldpi, n, q, Kit + m, l.ldm, st);
   if (rc) return rc;
-  const int mb = (m + 1 + q) + ((m + 1 + q) & 1);
   if (mb > m + 1 + q) GPMP_HIP_TRY(hipMemset2DAsync(Kit + m + 1 + q, (size_t)l.ldm * sizeof(double), 0, sizeof(double), n, st));
-  return potrf_trsm_lower_ws(K, n, l.ldn, ws + l.dinv, info_dev, Kit, mb, l.ldm, l.sws_elems ? ws + l.sws : nullptr, l.sws_elems, st);
+  double* sws = l.sws_elems ? ws + l.sws : nullptr;
+  if (f->hit())      // (the leaf scratch is this call's own, behind the block inverses of its dinv slot: hits may run side by side)
+    return trsm_lower_as_fused(f->K, n, l.ldn, f->dinv, ws + l.dinv + (size_t)((n + NB - 1) / NB) * NB * NB, Kit, mb, l.ldm, sws,
+                               l.sws_elems, st);
+  rc = potrf_trsm_lower_ws(f->K, n, l.ldn, f->dinv, info_dev, Kit, mb, l.ldm, sws, l.sws_elems, st);
+  return rc ? rc : factor_store_publish(&f->lease, info_dev);
 }
 }  // namespace
 }  // namespace gpmp
@@ -569,7 +605,8 @@ extern "C" int gpmp_nll_zero_mean(const double* x, const double* z, int n, int d
   const Cov cov(theta_host, d, p, noise);
   const DriverLayout l = driver_layout(n, 0, d, 0, USE_NLL);
   double* scal = ws + l.scal;
-  int rc = factor_and_whiten(cov, l, x, z, nullptr, 0, n, 0, ws, info_dev, stream);      // w = L^-1 z: n x 1, ld 16
+  Factor f;
+  int rc = factor_and_whiten(cov, l, x, z, nullptr, 0, n, 0, ws, info_dev, stream, true, &f);      // w = L^-1 z: n x 1, ld 16
   if (rc) return rc;
   rc = gpmp_coldots(ws + l.W, n, 1, l.ldq, nullptr, 0, 1, scal + 1, 1, ws + l.cd, stream);   // sum of squares of the one column
   if (rc) return rc;
@@ -596,7 +633,8 @@ extern "C" int gpmp_predict_zero_mean(const double* xi, const double* zi, const 
   const DriverLayout l = driver_layout(n, m, d, 0, USE_PREDICT);
   double* Kit = ws + l.Kit;
   double* D = ws + l.D;
-  int rc = predict_solve(cov, l, xi, zi, nullptr, 0, xt, n, m, 0, ws, info_dev, stream);
+  Factor f;
+  int rc = predict_solve(cov, l, xi, zi, nullptr, 0, xt, n, m, 0, ws, info_dev, stream, &f);
   if (rc) return rc;
   rc = gpmp_coldots(Kit, n, m, l.ldm, Kit + m, 1, l.ldm, D, l.ldm, ws + l.cd, stream);      // V^T w and colsumsq(V)
   if (rc) return rc;
@@ -618,7 +656,10 @@ extern "C" int gpmp_reml(const double* x, const double* z, const double* P, long
   GPMP_ARG(value_dev != nullptr, 12, "value_dev is NULL");
   const Cov cov(theta_host, d, p, noise);
   const DriverLayout l = driver_layout(n, 0, d, q, USE_REML);
-  rc = factor_and_meanspace(cov, l, x, z, P, ldp, n, q, ws, info_dev, stream);
+  Factor f;
+  rc = factor_and_whiten(cov, l, x, z, P, ldp, n, q, ws, info_dev, stream, true, &f);
+  if (rc) return rc;
+  rc = launch_meanspace(l, ws + l.W, l.ldq, P, ldp, n, q, ws, info_dev, stream);
   if (rc) return rc;
   return launch_reml_finalize(l, q, n, ws, info_dev, value_dev, as_stream(stream));
 }
@@ -718,7 +759,8 @@ extern "C" int gpmp_predict_mean(const double* xi, const double* zi, const doubl
   double* Kit = ws + l.Kit;
   double* W = Kit + m;
   const long ldw = l.ldm;
-  int rc = predict_solve(cov, l, xi, zi, Pi, ldpi, xt, n, m, q, ws, info_dev, stream);
+  Factor f;
+  int rc = predict_solve(cov, l, xi, zi, Pi, ldpi, xt, n, m, q, ws, info_dev, stream, &f);
   if (rc) return rc;
   rc = launch_meanspace(l, W, ldw, Pi, ldpi, n, q, ws, info_dev, stream);
   if (rc) return rc;
@@ -767,13 +809,14 @@ extern "C" int gpmp_predict_grad(const double* xi, const double* zi, const doubl
   hipStream_t st = as_stream(stream);
   const Cov cov(theta_host, d, p, noise);
   const DriverLayout l = driver_layout(n, m, d, q, USE_PREDICT_GRAD);
-  double* K = ws + l.K;
-  double* dinv = ws + l.dinv;
   double* Kit = ws + l.Kit;
   double* W = Kit + m;
   const long ldw = l.ldm;
-  int rc = predict_solve(cov, l, xi, zi, Pi, ldpi, xt, n, m, q, ws, info_dev, stream);
+  Factor f;
+  int rc = predict_solve(cov, l, xi, zi, Pi, ldpi, xt, n, m, q, ws, info_dev, stream, &f);
   if (rc) return rc;
+  const double* K = f.K;
+  const double* dinv = f.dinv;
   if (q > 0) {
     rc = launch_meanspace(l, W, ldw, Pi, ldpi, n, q, ws, info_dev, stream);
     if (rc) return rc;
@@ -833,7 +876,8 @@ extern "C" int gpmp_posterior_weights(const double* xi, const double* zi, const 
   hipStream_t st = as_stream(stream);
   const Cov cov(theta_host, d, p, noise);
   const DriverLayout l = driver_layout(n, 0, d, q, USE_WEIGHTS);
-  int rc = factor_and_whiten(cov, l, xi, zi, Pi, ldpi, n, q, ws, info_dev, stream);
+  Factor f;
+  int rc = factor_and_whiten(cov, l, xi, zi, Pi, ldpi, n, q, ws, info_dev, stream, true, &f);
   if (rc) return rc;
   if (q > 0) {
     rc = launch_meanspace(l, ws + l.W, l.ldq, Pi, ldpi, n, q, ws, info_dev, stream);
@@ -842,7 +886,7 @@ extern "C" int gpmp_posterior_weights(const double* xi, const double* zi, const 
   // alpha = K^-1 (z - P beta) = L^-T (w - Wp beta), beta = S^-1 Wp^T w
   hipLaunchKernelGGL(pgrad_gamma_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ws + l.W, l.ldq, n, q, ws + l.small, alpha_dev);
   GPMP_HIP_TRY(hipGetLastError());
-  rc = gpmp_trsm_lower(ws + l.K, n, l.ldn, ws + l.dinv, alpha_dev, 1, 1, 1, nullptr, stream);
+  rc = gpmp_trsm_lower(f.K, n, l.ldn, f.dinv, alpha_dev, 1, 1, 1, nullptr, stream);
   if (rc) return rc;
   const int len = n > q ? n : q;
   hipLaunchKernelGGL(weights_finalize_kernel, dim3((len + 255) / 256), dim3(256), 0, st, alpha_dev, n, beta_dev, q, ws + l.small,

@@ -9,6 +9,7 @@
 // Replaces numpy.linalg.cholesky / scipy.linalg.solve_triangular as used by gnp.cholesky_solve
 // (gpmp/num/numpy_backend.py:465-469) and diag_Kinv_from_chol (gpmp/core/linalg.py:17-46).
 #include "common.h"
+#include "factor_store.h"
 #include <vector>
 #include <cstdlib>
 #include <mutex>
@@ -220,10 +221,40 @@ struct LookAhead {
 // per device ordinal (round 4; rounds 1-3 kept one set and refused a second device), so a host that drives several GPUs from one
 // process -- one thread per GPU, each with its device current -- uses one copy of the library: threads on different devices do
 // not wait for each other, a second thread on the same device waits at that device's mutex (enqueueing takes microseconds).
+// HIP behind the factor store's bookkeeping (factor_store.h)
+struct HipStoreDev {
+  typedef hipStream_t Stream;
+  typedef hipEvent_t Event;
+  static int fail(hipError_t e, const char* what) { return e == hipSuccess ? 0 : hip_fail(e, what); }
+  static int alloc(void** p, size_t bytes) {
+    if (hipMalloc(p, bytes) == hipSuccess) return 0;
+    (void)hipGetLastError();           // out of memory is not an error of the call: the store is bypassed
+    return 1;
+  }
+  static void free(void* p) { (void)hipFree(p); }
+  static int event_create(Event* e) { return fail(hipEventCreateWithFlags(e, hipEventDisableTiming), "hipEventCreateWithFlags"); }
+  static void event_destroy(Event e) { (void)hipEventDestroy(e); }
+  static int event_record(Event e, Stream s) { return fail(hipEventRecord(e, s), "hipEventRecord"); }
+  static int stream_wait(Stream s, Event e) { return fail(hipStreamWaitEvent(s, e, 0), "hipStreamWaitEvent"); }
+  static int event_sync(Event e) { return fail(hipEventSynchronize(e), "hipEventSynchronize"); }
+  static int copy(void* dst, const void* src, size_t bytes, Stream s) {
+    return fail(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
+  }
+  static int compare(const double* x, const double* xcopy, size_t elems, const int* info, Stream s, int* flag_dev, int* differ) {
+    int rc = launch_bits_differ(x, xcopy, elems, info, flag_dev, s);
+    if (rc) return rc;
+    if ((rc = fail(hipMemcpyAsync(differ, flag_dev, sizeof(int), hipMemcpyDeviceToHost, s), "hipMemcpyAsync"))) return rc;
+    return fail(hipStreamSynchronize(s), "hipStreamSynchronize");
+  }
+};
+// (the mutex is recursive: a driver that holds a lease of the factor store keeps it while it enqueues its look-ahead factorisation)
 struct DeviceState {
   LookAhead la;
   hipStream_t solve_stream = nullptr;
-  std::mutex mu;
+  FactorStore<HipStoreDev> store;
+  size_t free_at_first_use = 0;        // device memory free when the store was first asked for: its default budget is a quarter
+  bool have_free = false;
+  std::recursive_mutex mu;
 };
 std::mutex g_dev_table_mu;
 std::map<int, std::shared_ptr<DeviceState>> g_dev_table;
@@ -323,19 +354,34 @@ constexpr int LA_LEAN_ABOVE = 4096;          // panel products take the small-fo
 constexpr int LA_SPLIT_ABOVE = 8192;         // look-ahead update of a 1024-column panel in three column pieces while more rows than this are left
 constexpr int LA_MAIN_AFTER_LA_BELOW = 4096; // at or below: a step's trailing update starts only after the next panel's look-ahead update
 
-int potrf_lookahead(double* A, int n, long lda, double* dinv, int* info_dev, hipStream_t s0, const SolveAlong* sa = nullptr) {
-  int dev = 0;
-  GPMP_HIP_TRY(hipGetDevice(&dev));
-  const std::shared_ptr<DeviceState> ds = device_state(dev);
-  std::lock_guard<std::mutex> la_lock(ds->mu);
-  LookAhead& g_la = ds->la;
-  hipStream_t& g_solve_stream = ds->solve_stream;
+// panel boundaries of the look-ahead factorisation, 0 = pb[0] < ... < pb.back() = n
+std::vector<int> lookahead_panels(int n) {
   std::vector<int> pb;
   for (int p = 0; p < n;) {
     pb.push_back(p);
     p += (n - p) > LA_WIDE_ABOVE ? 2 * OUTER_BLOCKS * NB : 2 * NB;
   }
   pb.push_back(n);
+  return pb;
+}
+// The solve along takes the rows of B in pieces of whole panels, each of at least along_piece_rows(n) rows
+// (a quarter of the matrix at a time measured best: 2048 -> 512, 4096 -> 1024, 8192 -> 2048 rows per piece)
+inline int along_piece_rows(int n) { return imax(OUTER_BLOCKS * NB, (n / 4) / (OUTER_BLOCKS * NB) * (OUTER_BLOCKS * NB)); }
+// end of the piece that starts at r0
+int along_piece_end(const std::vector<int>& pb, int r0, int along_rows, int n) {
+  for (size_t j = 0; j < pb.size(); ++j)
+    if (pb[j] > r0 && pb[j] - r0 >= along_rows) return pb[j];
+  return n;
+}
+
+int potrf_lookahead(double* A, int n, long lda, double* dinv, int* info_dev, hipStream_t s0, const SolveAlong* sa = nullptr) {
+  int dev = 0;
+  GPMP_HIP_TRY(hipGetDevice(&dev));
+  const std::shared_ptr<DeviceState> ds = device_state(dev);
+  std::lock_guard<std::recursive_mutex> la_lock(ds->mu);
+  LookAhead& g_la = ds->la;
+  hipStream_t& g_solve_stream = ds->solve_stream;
+  const std::vector<int> pb = lookahead_panels(n);
   const int np = (int)pb.size() - 1;
   if (g_la.helper == nullptr) {
     int lo = 0, hi = 0;
@@ -370,11 +416,7 @@ int potrf_lookahead(double* A, int n, long lda, double* dinv, int* info_dev, hip
   // (round 1 issued (a) and (b) together behind the piece's last panel: kernel trace at n = 4096, m = 10000: 1.75 ms of solve
   //  after the last panel, of which 0.83 ms was that piece's (a).)
   int along_rows = 0, upd_end = 0;              // rows < upd_end belong to the piece whose (b) comes next
-  auto piece_end = [&](int r0) {
-    for (size_t j = 0; j < pb.size(); ++j)
-      if (pb[j] > r0 && pb[j] - r0 >= along_rows) return pb[j];
-    return n;
-  };
+  auto piece_end = [&](int r0) { return along_piece_end(pb, r0, along_rows, n); };
   int solved_from = 0;                           // start of the piece solved last
   auto early_update = [&](int r0) -> int {       // (a) behind the piece that ends at r0 = n1_solved
     if (r0 >= n) return 0;
@@ -386,8 +428,7 @@ int potrf_lookahead(double* A, int n, long lda, double* dinv, int* info_dev, hip
     return rcu;
   };
   if (sa != nullptr) {
-    // (a quarter of the matrix at a time measured best: 2048 -> 512, 4096 -> 1024, 8192 -> 2048 rows per piece)
-    along_rows = imax(OUTER_BLOCKS * NB, (n / 4) / (OUTER_BLOCKS * NB) * (OUTER_BLOCKS * NB));
+    along_rows = along_piece_rows(n);
     GPMP_HIP_TRY(hipStreamWaitEvent(g_solve_stream, e_f, 0));
     rc = trsm_forward(A, pb[1], lda, dinv, sa->B, sa->m, sa->ldb, sa->gws, g_solve_stream);
     if (rc) return rc;
@@ -725,11 +766,12 @@ int release_device_state(int dev) {
     ds = std::move(it->second);
     g_dev_table.erase(it);
   }
-  std::lock_guard<std::mutex> lk(ds->mu);          // an enqueue section still running on another thread finishes first
+  std::lock_guard<std::recursive_mutex> lk(ds->mu);          // an enqueue section still running on another thread finishes first
   // (streams are synchronised before they go: their kernels may still be running.)  Every handle is released whatever the
   // earlier ones answered; the first error is what the caller gets.
   hipError_t first = hipSuccess;
   auto note = [&](hipError_t e) { if (e != hipSuccess && first == hipSuccess) first = e; };
+  const int store_rc = ds->store.release();        // waits for the stored factor's factorisation and its readers, then frees it
   for (hipStream_t* st : {&ds->la.helper, &ds->la.side, &ds->solve_stream})
     if (*st != nullptr) {
       note(hipStreamSynchronize(*st));
@@ -739,7 +781,8 @@ int release_device_state(int dev) {
   for (hipEvent_t e : ds->la.pool) note(hipEventDestroy(e));
   ds->la.pool.clear();
   ds->la.used = 0;
-  return first == hipSuccess ? 0 : hip_fail(first, "gpmp_device_release");
+  if (first != hipSuccess) return hip_fail(first, "gpmp_device_release");
+  return store_rc;
 }
 }  // namespace
 }  // namespace gpmp
@@ -770,7 +813,7 @@ extern "C" int gpmp_debug_device_table_selftest(int threads, int ordinals, int i
       for (int it = 0; it < iters; ++it)
         for (int o = 0; o < ordinals; ++o) {
           const std::shared_ptr<DeviceState> ds = device_state(1000 + (o + t) % ordinals);
-          std::lock_guard<std::mutex> lk(ds->mu);           // what an enqueue section does
+          std::lock_guard<std::recursive_mutex> lk(ds->mu);           // what an enqueue section does
           ds->la.used = 0;
           DeviceState*& slot = seen[t][(o + t) % ordinals];
           if (slot == nullptr) slot = ds.get();
@@ -837,6 +880,99 @@ extern "C" int gpmp_debug_strassen_update(const double* L21, long ldl, const dou
   return strassen_update(L21, ldl, X1, ldx, B2, ldb, R, R, N, scratch, as_stream(stream));
 }
 
+// the route of potrf_trsm_lower_ws: rows of B solved behind their panels (SolveAlong) instead of after the factorisation
+static inline bool solve_goes_along(int n, int m, size_t strassen_need) {
+  constexpr int along_above = 2 * OUTER_BLOCKS * NB, along_below = 8192;
+  return strassen_need == 0 && m > TRSV_FEW_MAX && n > along_above && n <= along_below;
+}
+
+int gpmp::trsm_lower_as_fused(const double* L, int n, long ldl, const double* dinv, double* gws, double* B, int m, long ldb, double* sws,
+                              size_t sws_elems, hipStream_t st) {
+  if (n <= 0 || m <= 0) return 0;
+  StrassenWs sw;
+  sw.lim = strassen_limits();
+  const size_t sneed = (sws != nullptr && m > TRSV_FEW_MAX) ? strassen_solve_elems(n, m, sw.lim) : 0;
+  GPMP_ARG(sws_elems >= sneed, 10, "Strassen scratch below gpmp_strassen_ws_elems(n, m)");
+  if (sneed > 0) { sw.p = sws; sw.elems = sws_elems; }
+  if (n <= 2 * OUTER_BLOCKS * NB) gws = nullptr;
+  if (!solve_goes_along(n, m, sneed)) {
+    if (m <= TRSV_FEW_MAX) return trsv_few(L, n, ldl, dinv, B, m, ldb, 0, st);
+    return trsm_forward(L, n, ldl, dinv, B, m, ldb, gws, st, sneed > 0 ? &sw : nullptr);
+  }
+  // the pieces of potrf_lookahead's solve along, one after the other: diagonal solve of the piece, then its contribution to every
+  // later row at once
+  const std::vector<int> pb = lookahead_panels(n);
+  const int along_rows = along_piece_rows(n);
+  for (int r0 = 0, r1 = pb[1]; r0 < n; r0 = r1, r1 = along_piece_end(pb, r0, along_rows, n)) {
+    int rc = trsm_forward(L + (long)r0 * ldl + r0, r1 - r0, ldl, dinv + (size_t)(r0 / NB) * NB * NB, B + (long)r0 * ldb, m, ldb, gws, st);
+    if (rc) return rc;
+    if (r1 < n) {
+      GemmOpts plain;
+      rc = launch_gemm(true, false, n - r1, m, r1 - r0, -1.0, L + (long)r1 * ldl + r0, ldl, B + (long)r0 * ldb, ldb, 1.0,
+                       B + (long)r1 * ldb, ldb, plain, st);
+      if (rc) return rc;
+    }
+  }
+  return 0;
+}
+
+// ---- the factor store: HIP glue around FactorStore (factor_store.h) -------------------------------------------------------------
+int gpmp::factor_route(int n, int m, bool have_sws) {
+  const size_t sneed = (have_sws && m > TRSV_FEW_MAX) ? strassen_solve_elems(n, m, strassen_limits()) : 0;
+  return (solve_goes_along(n, m, sneed) || n > POTRF_ONE_STREAM_MAX) ? 1 : 0;
+}
+
+int gpmp::factor_store_acquire(const double* x, int n, int d, int p, int noise, const double* theta_host, double diag, long ldn,
+                               int route, hipStream_t st, FactorLease* lease) {
+  const char* env = getenv("GPMP_FACTOR_STORE_MB");
+  int dev = 0;
+  GPMP_HIP_TRY(hipGetDevice(&dev));
+  if (env != nullptr && factor_store_budget(env, 0) == 0) {
+    // disabled: nothing is created; a factor kept from before the switch was set goes, with its memory
+    std::shared_ptr<DeviceState> held;
+    {
+      std::lock_guard<std::mutex> lk(g_dev_table_mu);
+      auto it = g_dev_table.find(dev);
+      if (it != g_dev_table.end()) held = it->second;
+    }
+    if (held == nullptr) return 0;
+    std::lock_guard<std::recursive_mutex> lk(held->mu);
+    return held->store.release();
+  }
+  // a stream under capture cannot be waited for, which the key check does
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  GPMP_HIP_TRY(hipStreamIsCapturing(st, &cap));
+  if (cap != hipStreamCaptureStatusNone) return 0;
+  std::shared_ptr<DeviceState> ds = device_state(dev);
+  std::unique_lock<std::recursive_mutex> lock(ds->mu);
+  if (!ds->have_free) {
+    size_t free_b = 0, total_b = 0;
+    GPMP_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    ds->free_at_first_use = free_b;
+    ds->have_free = true;
+  }
+  const size_t dinv_elems = gpmp_dinv_elems(n);
+  const std::vector<unsigned char> key = factor_key_bytes(n, d, p, noise, ldn, dinv_elems, route, diag, theta_host);
+  int mode = 0;
+  const int rc = ds->store.acquire(key, x, (size_t)n * d, (size_t)n * ldn, dinv_elems, factor_store_budget(env, ds->free_at_first_use), st,
+                                   &mode, &lease->L, &lease->dinv);
+  if (rc || mode == 0) return rc;
+  lease->mode = mode;
+  lease->st = st;
+  lease->owner = ds;
+  lease->lock = std::move(lock);
+  return 0;
+}
+
+int gpmp::factor_store_publish(FactorLease* lease, const int* info_dev) {
+  if (lease->mode != 2) return 0;
+  return static_cast<DeviceState*>(lease->owner.get())->store.publish(info_dev, lease->st);
+}
+
+gpmp::FactorLease::~FactorLease() {
+  if (mode != 0) (void)static_cast<DeviceState*>(owner.get())->store.done(st);
+}
+
 extern "C" int gpmp_potrf_trsm_lower_async(double* A, int n, long lda, double* dinv, int* info_dev, double* B, int m, long ldb,
                                            gpmp_stream_t stream) {
   return potrf_trsm_lower_ws(A, n, lda, dinv, info_dev, B, m, ldb, nullptr, 0, as_stream(stream));
@@ -865,8 +1001,7 @@ int gpmp::potrf_trsm_lower_ws(double* A, int n, long lda, double* dinv, int* inf
   // n = 4096), so the rows of every piece of panels are solved behind those panels' factorisation on a third stream (SolveAlong).
   // Above that the solve follows the factorisation on the caller's stream: overlapping its leading half with the trailing half of
   // the factorisation gained 5-7 ms of a 950 ms call (two GEMM streams lose ~7 % to each other) and was dropped.
-  constexpr int along_above = 2 * OUTER_BLOCKS * NB, along_below = 8192;
-  if (sneed == 0 && m > TRSV_FEW_MAX && n > along_above && n <= along_below) {
+  if (solve_goes_along(n, m, sneed)) {
     SolveAlong sa;
     sa.B = B; sa.m = m; sa.ldb = ldb; sa.gws = gws;
     return potrf_lookahead(A, n, lda, dinv, info_dev, st, &sa);

@@ -163,7 +163,27 @@ __global__ void __launch_bounds__(256) block_sum_kernel(const double* __restrict
   }
 }
 
+// The factor store's key check (factor_store.h): *flag = 1 unless a and b agree as 64-bit patterns and *info == 0.
+__global__ void bits_flag_init_kernel(const int* __restrict__ info, int* __restrict__ flag) { *flag = (*info != 0) ? 1 : 0; }
+__global__ void __launch_bounds__(256) bits_differ_kernel(const unsigned long long* __restrict__ a, const unsigned long long* __restrict__ b,
+                                                          size_t elems, int* __restrict__ flag) {
+  bool differ = false;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < elems; i += (size_t)gridDim.x * 256) differ |= a[i] != b[i];
+  if (differ) *flag = 1;
+}
+
 }  // namespace
+
+int launch_bits_differ(const double* a, const double* b, size_t elems, const int* info, int* flag, hipStream_t st) {
+  hipLaunchKernelGGL(bits_flag_init_kernel, dim3(1), dim3(1), 0, st, info, flag);
+  GPMP_HIP_TRY(hipGetLastError());
+  if (elems == 0) return 0;
+  const size_t want = (elems + 255) / 256, most = (size_t)16 * device_cu_count();
+  hipLaunchKernelGGL(bits_differ_kernel, dim3((unsigned)(want < most ? want : most)), dim3(256), 0, st,
+                     reinterpret_cast<const unsigned long long*>(a), reinterpret_cast<const unsigned long long*>(b), elems, flag);
+  GPMP_HIP_TRY(hipGetLastError());
+  return 0;
+}
 
 int launch_block_sum(const double* X, long ldx, const double* Y, long ldy, double sign, double* D, long ldd, int rows, int cols,
                      hipStream_t st) {

@@ -190,8 +190,11 @@ int gpmp_solve_status(gpmp_stream_t stream, int* status_host);
  * single-vector solves; a later solve on the same handle simply allocates a fresh block. */
 int gpmp_stream_release(gpmp_stream_t stream);
 /* Per-device host state (helper streams / events of the look-ahead factorisation; created at a device's first large
- * factorisation).  gpmp_device_release: synchronises and destroys what the CURRENT device holds (0 if nothing; the next
- * factorisation on it creates fresh ones).  gpmp_device_state_count: devices that hold such state (host only, no HIP call).
+ * factorisation; and the factor store: the newest Cholesky factor of K(xi, xi; theta) that gpmp_predict_zero_mean,
+ * gpmp_predict_mean, gpmp_predict_grad, gpmp_nll_zero_mean, gpmp_reml or gpmp_posterior_weights computed on the device, in
+ * memory the library owns -- budget GPMP_FACTOR_STORE_MB megabytes, default a quarter of the memory free at first use and at
+ * most 32 GiB, 0 = no store).  gpmp_device_release: synchronises and destroys what the CURRENT device holds, the stored factor
+ * included (0 if nothing; the next factorisation on it creates fresh ones).  gpmp_device_state_count: devices that hold such state (host only, no HIP call).
  * gpmp_debug_device_table_selftest: host-only consistency check of that table under `threads` concurrent host threads
  * (made-up ordinals, no HIP call; 0 = consistent) -- what tests/test_asan_cpu.py runs under ASan + UBSan.
  * No counterpart in the reference (single-threaded Python, no device code). */
@@ -281,7 +284,10 @@ size_t gpmp_grad_ws_elems(int n, int d);
  * the whole of negative_log_likelihood_zero_mean (gpmp/core/likelihood.py:18-52) -- Gram build, Cholesky,
  * one triangular solve, two reductions -- enqueued by one call.  x: n x d row-major, z: n, both on the device.
  * *info_dev as gpmp_potrf_lower_async; when it is non-zero *nll_dev = +inf (the reference returns safe_inf(),
- * likelihood.py:47-48).  ws: gpmp_nll_ws_elems(n) doubles (holds K / L on return).  Enqueue only. */
+ * likelihood.py:47-48).  ws: gpmp_nll_ws_elems(n) doubles.  The factor store (below, GPMP_FACTOR_STORE_MB): when x, n, d, p,
+ * theta and noise are bit for bit those of the factor the library keeps for this device, the Gram build and the Cholesky are
+ * skipped and L is read from the store -- the result has the same bits either way; the check reads one word back (a stream
+ * synchronise).  Otherwise the call only enqueues, and factors into the store (or, above its budget, into ws). */
 size_t gpmp_nll_ws_elems(int n);
 int gpmp_nll_zero_mean(const double* x, const double* z, int n, int d, int p, const double* theta_host,
                        int noise, double* ws, double* nll_dev, int* info_dev, gpmp_stream_t stream);
@@ -398,7 +404,7 @@ int gpmp_predict_grad(const double* xi, const double* zi, const double* Pi, long
  * gpmp_posterior_weights: Gram build, Cholesky, W = L^-1 [zi, Pi], the q x q algebra and one back solve, as the drivers above;
  * alpha_dev (n) and beta_dev (q; may be NULL only when q = 0) are device vectors.  Pi: n x q (ldpi), 0 <= q < GPMP_MAX_RANK,
  * n > q, 1 <= d <= GPMP_MAX_DIM_WIDE.  *info_dev as gpmp_predict_mean; when it is non-zero alpha and beta are NaN.
- * ws: gpmp_posterior_weights_ws_elems(n, q) doubles (holds L on return).  Enqueue only. */
+ * ws: gpmp_posterior_weights_ws_elems(n, q) doubles.  Enqueue only, except for the factor store's check (gpmp_nll_zero_mean). */
 size_t gpmp_posterior_weights_ws_elems(int n, int q);
 int gpmp_posterior_weights(const double* xi, const double* zi, const double* Pi, long ldpi, int n, int d, int q, int p,
                            const double* theta_host, int noise, double* ws, double* alpha_dev, double* beta_dev,
