@@ -20,7 +20,8 @@
 // device, so no driver ever waits for the host.  The mean design P = mean(xi) (n x q, row-major) is passed in: mean
 // functions are user callables in the reference (gpmp/core/model.py:30-52).
 // The host side of the nine drivers is built from the shared steps below the kernels: one workspace layout, the covariance
-// setup, factor_and_whiten, predict_solve, launch_meanspace, solve_back, launch_reml_finalize.
+// setup, factor_plain, whiten_cols, factor_and_whiten, predict_solve, launch_meanspace, solve_back, launch_reml_finalize.  gpmp_whiten
+// is the first two on their own, for the Python likelihood, which finishes the sum itself.
 #include "matern_device.h"
 
 namespace gpmp {
@@ -438,6 +439,17 @@ constexpr unsigned USE_PREDICT_GRAD = WS_KIT | WS_MEAN | WS_PGRAD;
 constexpr unsigned USE_WEIGHTS = WS_W | WS_MEAN | WS_SCAL;     // the weights land in the caller's vectors: no X, no y slot
 constexpr unsigned USE_WEIGHTS_MULTI = WS_MEAN | WS_COLS;
 
+// gpmp_whiten keeps its columns in the caller's matrix: the K and dinv slots alone, where every layout has them (no cd)
+DriverLayout whiten_layout(int n) {
+  DriverLayout l = {};
+  l.ldn = pad16(n);
+  WsCursor c;
+  l.K = c.take((size_t)n * l.ldn);
+  l.dinv = c.take(gpmp_dinv_elems(n));
+  l.total = c.at;
+  return l;
+}
+
 // The covariance as the drivers hand it on.  Built only after the argument checks have passed theta_host.
 struct Cov {
   const double* theta;
@@ -491,28 +503,37 @@ int locate_factor(const Cov& cov, const DriverLayout& l, const double* x, int n,
   return 0;
 }
 
-// Gram (lower) -> Cholesky -> W = L^-1 [z, P] -> ln|K|.  Leaves L in f->K, W in ws + l.W, ln|K| in ws + l.scal.  On a hit of the
-// factor store the first two steps are skipped; the info word is cleared as the factorisation would have.
-int factor_and_whiten(const Cov& cov, const DriverLayout& l, const double* x, const double* z, const double* P, long ldp, int n,
-                      int q, double* ws, int* info_dev, gpmp_stream_t stream, bool store, Factor* f) {
+// Gram (lower) -> Cholesky by the plain potrf's route.  Leaves L in f->K.  On a hit of the factor store both steps are skipped; the
+// info word is cleared as the factorisation would have.  Of the layout only ldn, K and dinv are read.
+int factor_plain(const Cov& cov, const DriverLayout& l, const double* x, int n, double* ws, int* info_dev, gpmp_stream_t stream,
+                 bool store, Factor* f) {
   int rc = locate_factor(cov, l, x, n, factor_route(n, 0, false), ws, store, as_stream(stream), f);
   if (rc) return rc;
-  double* W = ws + l.W;
   if (f->hit()) {
     GPMP_HIP_TRY(hipMemsetAsync(info_dev, 0, sizeof(int), as_stream(stream)));
-  } else {
-    rc = gpmp_matern_gram(x, nullptr, n, n, cov.d, cov.p, cov.theta, cov.noise, cov.diag, 1, f->K, l.ldn, stream);
-    if (rc) return rc;
-    rc = gpmp_potrf_lower_async(f->K, n, l.ldn, f->dinv, info_dev, stream);
-    if (rc) return rc;
-    rc = factor_store_publish(&f->lease, info_dev);
-    if (rc) return rc;
+    return 0;
   }
-  rc = stage_zp(z, P, ldp, n, q, W, l.ldq, as_stream(stream));
+  rc = gpmp_matern_gram(x, nullptr, n, n, cov.d, cov.p, cov.theta, cov.noise, cov.diag, 1, f->K, l.ldn, stream);
   if (rc) return rc;
-  rc = gpmp_trsm_lower(f->K, n, l.ldn, f->dinv, W, 1 + q, l.ldq, 0, nullptr, stream);
+  rc = gpmp_potrf_lower_async(f->K, n, l.ldn, f->dinv, info_dev, stream);
   if (rc) return rc;
-  return gpmp_logdet_chol(f->K, n, l.ldn, ws + l.scal, stream);
+  return factor_store_publish(&f->lease, info_dev);
+}
+
+// Y <- L^-1 Y (n x ncols, ncols <= TRSV_FEW_MAX: the few-column sweep, whatever scratch there is) and *logdet = ln|K|
+int whiten_cols(const Factor& f, int n, long ldn, double* Y, int ncols, long ldy, double* logdet, gpmp_stream_t stream) {
+  const int rc = gpmp_trsm_lower(f.K, n, ldn, f.dinv, Y, ncols, ldy, 0, nullptr, stream);
+  return rc ? rc : gpmp_logdet_chol(f.K, n, ldn, logdet, stream);
+}
+
+// Gram (lower) -> Cholesky -> W = L^-1 [z, P] -> ln|K|.  Leaves L in f->K, W in ws + l.W, ln|K| in ws + l.scal.
+int factor_and_whiten(const Cov& cov, const DriverLayout& l, const double* x, const double* z, const double* P, long ldp, int n,
+                      int q, double* ws, int* info_dev, gpmp_stream_t stream, bool store, Factor* f) {
+  int rc = factor_plain(cov, l, x, n, ws, info_dev, stream, store, f);
+  if (rc) return rc;
+  rc = stage_zp(z, P, ldp, n, q, ws + l.W, l.ldq, as_stream(stream));
+  if (rc) return rc;
+  return whiten_cols(*f, n, l.ldn, ws + l.W, 1 + q, l.ldq, ws + l.scal, stream);
 }
 
 // Gram of W = L^-1 [z, P] (n x (1 + q), leading dimension ldw) and, with a mean design, P^T P and the q x q algebra.
@@ -613,6 +634,28 @@ extern "C" int gpmp_nll_zero_mean(const double* x, const double* z, int n, int d
   hipLaunchKernelGGL(nll_finalize_kernel, dim3(1), dim3(1), 0, as_stream(stream), scal, scal + 1, info_dev, n, nll_dev);
   GPMP_HIP_TRY(hipGetLastError());
   return 0;
+}
+
+extern "C" size_t gpmp_whiten_ws_elems(int n) { return (n > 0 && n <= GPMP_MAX_EXTENT) ? whiten_layout(n).total : 0; }
+
+extern "C" int gpmp_whiten(const double* x, int n, int d, int p, const double* theta_host, int noise, double* Y, int ncols, long ldy,
+                           double* ws, double* logdet_dev, int* info_dev, gpmp_stream_t stream) {
+  GPMP_ARG(x != nullptr, 1, "x is NULL");
+  GPMP_ARG(n > 0 && n <= GPMP_MAX_EXTENT, 2, "n outside [1, GPMP_MAX_EXTENT]");
+  GPMP_ARG(d >= 1 && d <= GPMP_MAX_DIM_WIDE, 3, "d outside [1, GPMP_MAX_DIM_WIDE]");
+  GPMP_ARG(p >= 0 && p <= GPMP_MAX_P, 4, "p outside [0, GPMP_MAX_P]");
+  GPMP_ARG(theta_host != nullptr, 5, "theta is NULL");
+  GPMP_ARG(Y != nullptr, 7, "Y is NULL");
+  GPMP_ARG(ncols >= 1 && ncols <= TRSV_FEW_MAX, 8, "ncols outside [1, 16]");
+  GPMP_ARG(ldy >= ncols, 9, "ldy < ncols");
+  GPMP_ARG(ws != nullptr, 10, "ws is NULL");
+  GPMP_ARG(logdet_dev != nullptr, 11, "logdet_dev is NULL");
+  GPMP_ARG(info_dev != nullptr, 12, "info_dev is NULL");
+  const Cov cov(theta_host, d, p, noise);
+  const DriverLayout l = whiten_layout(n);
+  Factor f;
+  const int rc = factor_plain(cov, l, x, n, ws, info_dev, stream, true, &f);
+  return rc ? rc : whiten_cols(f, n, l.ldn, Y, ncols, ldy, logdet_dev, stream);     // (the lease ends behind both, with f)
 }
 
 extern "C" size_t gpmp_predict_ws_elems(int n, int m) { return (n > 0 && m > 0) ? driver_layout(n, m, 1, 0, USE_PREDICT).total : 0; }

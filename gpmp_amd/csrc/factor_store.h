@@ -1,6 +1,8 @@
 // The factor store: at most ONE Cholesky factor of K(xi, xi; theta) per device, kept across calls of the fused drivers (drivers.hip).
 // A call whose observation points and covariance parameters are exactly those of the stored factor skips the Gram build and the
-// factorisation and reads L from here (GPMP_FACTOR_STORE_MB).
+// factorisation and reads L from here (GPMP_FACTOR_STORE_MB).  Its readers are the drivers that leave L as it
+// is -- the predictions, gpmp_nll_zero_mean, gpmp_reml, gpmp_posterior_weights -- and gpmp_whiten, through which the Python zero-mean
+// likelihood (core/likelihood.py) finds the factor a prediction or an earlier evaluation on the same data left here.
 // This header is host-only C++ without a HIP include: every device operation goes through the policy class `Dev`, which linalg.hip
 // fills with HIP calls and tests/factor_store_host.cpp with host stand-ins, so the bookkeeping below runs under the host sanitizers.
 #pragma once

@@ -191,7 +191,7 @@ int gpmp_solve_status(gpmp_stream_t stream, int* status_host);
 int gpmp_stream_release(gpmp_stream_t stream);
 /* Per-device host state (helper streams / events of the look-ahead factorisation; created at a device's first large
  * factorisation; and the factor store: the newest Cholesky factor of K(xi, xi; theta) that gpmp_predict_zero_mean,
- * gpmp_predict_mean, gpmp_predict_grad, gpmp_nll_zero_mean, gpmp_reml or gpmp_posterior_weights computed on the device, in
+ * gpmp_predict_mean, gpmp_predict_grad, gpmp_nll_zero_mean, gpmp_whiten, gpmp_reml or gpmp_posterior_weights computed on the device, in
  * memory the library owns -- budget GPMP_FACTOR_STORE_MB megabytes, default a quarter of the memory free at first use and at
  * most 32 GiB, 0 = no store).  gpmp_device_release: synchronises and destroys what the CURRENT device holds, the stored factor
  * included (0 if nothing; the next factorisation on it creates fresh ones).  gpmp_device_state_count: devices that hold such state (host only, no HIP call).
@@ -291,6 +291,24 @@ size_t gpmp_grad_ws_elems(int n, int d);
 size_t gpmp_nll_ws_elems(int n);
 int gpmp_nll_zero_mean(const double* x, const double* z, int n, int d, int p, const double* theta_host,
                        int noise, double* ws, double* nll_dev, int* info_dev, gpmp_stream_t stream);
+
+/* The first half of the above for a caller that finishes the sum itself (gpmp_amd/core/likelihood.py, whose torch reduction
+ * rounds differently from the column-dot kernel): Y <- L^-1 Y in place and *logdet_dev = ln|K|, with L the Cholesky factor of
+ * K = gpmp_matern_gram(x) + nugget (or noise variance) -- Gram build, gpmp_potrf_lower_async, gpmp_trsm_lower (the
+ * few-column sweep), gpmp_logdet_chol, enqueued by one call.  x: n x d row-major; Y: n x ncols row-major, leading dimension
+ * ldy >= ncols, 1 <= ncols <= 16; theta_host: 1 + noise + d doubles on the host; 1 <= d <= GPMP_MAX_DIM_WIDE, 0 <= p <=
+ * GPMP_MAX_P.  *info_dev as gpmp_potrf_lower_async; when it is non-zero Y and *logdet_dev mean nothing.
+ * ws: gpmp_whiten_ws_elems(n) = pad16(n pad16(n)) + pad16(gpmp_dinv_elems(n)) doubles (0 for n <= 0 or above
+ * GPMP_MAX_EXTENT): room for L and its block inverses, used only when the store does not take them.
+ * The factor store (GPMP_FACTOR_STORE_MB), with the route of the plain gpmp_potrf_lower_async in the key: when x, n, d, p, theta
+ * and noise are bit for bit those of the stored factor and that factor came from the same schedule, no Gram build and no
+ * factorisation run, *info_dev is cleared and L is read from the store -- Y and *logdet_dev have the bits the caller's own
+ * factorisation would have given; the check reads one word back (the one stream synchronise of a call).  Otherwise the call
+ * only enqueues: it factors into the store's buffer and publishes it, or, with the store off or the factor above its budget,
+ * factors in ws.  The store is held until the solve and the log-determinant are enqueued. */
+size_t gpmp_whiten_ws_elems(int n);
+int gpmp_whiten(const double* x, int n, int d, int p, const double* theta_host, int noise, double* Y, int ncols, long ldy,
+                double* ws, double* logdet_dev, int* info_dev, gpmp_stream_t stream);
 
 /* Posterior mean and variance at m points: kriging_predictor_with_zero_mean + _compute_posterior_variance
  * (gpmp/core/kriging.py:35-67,170-199) restated as ONE solve  V = L^-1 K(xi, xt) (gpmp_potrf_trsm_lower_async):
