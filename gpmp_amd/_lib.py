@@ -88,6 +88,8 @@ SIGNATURES = {
     "gpmp_posterior_mean_wide_ws_elems": (c_size_t, [c_int, c_int, c_int, c_int]),
     "gpmp_posterior_mean_wide": (c_int, [_P, _P, c_long, _P, _P, c_long, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int,
                                          _P, _P, c_long, _P]),
+    "gpmp_fourier_paths_ws_elems": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "gpmp_fourier_paths": (c_int, [_P, _P, c_long, _P, _P, c_long, c_int, c_int, c_int, c_int, _P, _P, c_long, _P]),
     "gpmp_reml_ws_elems": (c_size_t, [c_int, c_int]),
     "gpmp_reml": (c_int, [_P, _P, _P, c_long, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P]),
     "gpmp_nll_grad_ws_elems": (c_size_t, [c_int, c_int, c_int]),

@@ -159,6 +159,25 @@ class Model:
     def sample_paths(self, xt, nb_paths, method="chol", check_result=True):
         return sample_paths.sample_paths(self, xt, nb_paths, method=method, check_result=check_result)
 
+    def prior_paths(self, nb_paths, nb_features=4096, seed=None):
+        """``nb_paths`` prior sample paths as FUNCTIONS (``core.fourier_paths.PriorPaths``): each a trigonometric sum over
+        ``nb_features`` random frequencies drawn on the host from the spectral measure of the Matern covariance (``seed``: the same
+        paths on any machine).  ``prior.paths(xt)`` is (m, nb_paths) at any points, one launch, no dense covariance; the law of a
+        path is Gaussian with a covariance within O(nb_features^-1/2) of the model's.  Matern covariances only."""
+        from .fourier_paths import PriorPaths
+
+        return PriorPaths(self, nb_paths, nb_features, seed)
+
+    def posterior_paths(self, xi, zi, nb_paths, nb_features=4096, seed=None, convert_in=True):
+        """``nb_paths`` posterior sample paths given (xi, zi) as functions (``core.fourier_paths.PosteriorPaths``): the prior paths
+        of ``prior_paths`` plus the exact matrix-free update of ``conditional_sample_paths_from_data`` -- one factorisation here,
+        then ``post.paths(xt)`` is (m, nb_paths) at any points.  With a noise parameter the observations are perturbed per path
+        (``post.eps``).  Zero, parameterized and linear-predictor means."""
+        from .fourier_paths import PosteriorPaths
+
+        xi, zi, _ = utils.ensure_shapes_and_type(xi=xi, zi=zi, convert=convert_in)
+        return PosteriorPaths(self, xi, zi, nb_paths, nb_features, seed)
+
     def conditional_sample_paths(self, ztsim, xi_ind, zi, xt_ind, lambda_t, convert_out=True):
         return sample_paths.conditional_sample_paths(self, ztsim, xi_ind, zi, xt_ind, lambda_t, convert_out=convert_out)
 

@@ -504,6 +504,20 @@ int gpmp_posterior_mean_wide(const double* xi, const double* A, long lda, const 
                              const double* B, long ldb, int n, int m, int s, int d, int q, int p,
                              const double* theta_host, int noise, double* ws, double* O_dev, long ldo, gpmp_stream_t stream);
 
+/* ---- function-space sample paths: random Fourier features, evaluated without the m x r feature block ----------------------
+ * gpmp_fourier_paths: out[t][c] = sum_{k<r} cos(2 pi (sum_{j<d} xt[t][j] omega[k][j] + phase[k])) W[k][c]      (m x s, ldo >= s)
+ * xt: m x d (row stride d); omega: r x d (ldomega >= d); phase: r; W: r x s (ldw >= s); all fp64, row-major, device memory.
+ * Frequencies and phases are in TURNS (cycles), so the argument reduction u - rint(u) is exact in fp64; the cosine itself has an
+ * absolute error of at most 4 * 2^-52.  One launch: the phases by fp64 matrix instructions over d (phase[k] the initial
+ * accumulator), the cosines on the accumulators in registers, the contraction against W by the same instruction; no m x r block is
+ * stored.  Nothing beyond column d of a row of xt or omega, or column s of a row of W or out, is read or written.
+ * 1 <= d <= GPMP_MAX_DIM_WIDE (d is streamed); 1 <= s <= GPMP_MAX_COLUMNS; 1 <= m, r <= GPMP_MAX_EXTENT.  When m is small the sum
+ * over k is split into slices that are added in a fixed order (no atomics): two calls on the same inputs give the same bits.
+ * ws: gpmp_fourier_paths_ws_elems(m, r, s, d) doubles (0 for arguments out of range).  Enqueue only. */
+size_t gpmp_fourier_paths_ws_elems(int m, int r, int s, int d);
+int gpmp_fourier_paths(const double* xt, const double* omega, long ldomega, const double* phase, const double* W, long ldw,
+                       int m, int r, int s, int d, double* ws, double* out, long ldo, gpmp_stream_t stream);
+
 /* ---- many small problems at once (mini-batch criteria, posterior samplers) ------------------------------------- */
 
 /* B independent criteria -- the zero-mean NLL (q = 0) or REML with a mean design of q <= GPMP_BATCH_MAX_Q columns -- and, when
